@@ -10,10 +10,16 @@ timed region.  Weak scaling: per-GPU work is fixed, N GPUs solve N x 4096
 targets (N = 8 is 32768 targets; `--swarms-per-gpu 8192` gives config 4's
 65536).  Generator seeds are global (swarm b, particle i: curand_init(b*1024+i)).
 
-With the default config 3 the same run also times, every rank, the other
-BASELINE lines under "legs": config 4's shard (8192 targets per GPU, so N = 8
-is the named 65536), config 5 at its named size (8192 targets of the 20-joint
-chain over all GPUs) and the DH arm (dh7); `--extra-steps 0` skips them.
+A plain run sets up, warms up, times `--steps` steps, writes the last step's
+results if `--dump-outputs DIR` is given and prints the line: the headline
+figures (`value`, `ms_per_step`, ...) and the roofline priced from the committed
+counters.  Everything that takes runs of its own is behind `--full`: the CPU
+baseline, the single-solve latency, the REFERENCE-arithmetic leg, the
+visualiser frame latency and, with the default config 3, the other BASELINE
+lines timed on every rank under "legs": config 4's shard (8192 targets per GPU,
+so N = 8 is the named 65536), config 5 at its named size (8192 targets of the
+20-joint chain over all GPUs), the DH arm (dh7) and the collider term;
+`--extra-steps 0` skips the legs.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md for every field).
 """
@@ -58,20 +64,29 @@ def parse():
                          "four, or all four moved 1000 units away (the collider kernel with nothing near)")
     ap.add_argument("--kernel", choices=["auto", "resident", "coop", "streaming"], default="auto",
                     help="kernel family (auto: resident if the swarm fits one workgroup, else cooperative)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="bounded CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU baseline, the single-solve latency, "
+                         "the REFERENCE-arithmetic leg, the frame latency and the extra legs (the options below "
+                         "size them; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the gathered per-swarm "
+                         "results on the host) as DIR/angles.npy, DIR/fitness.npy and DIR/residual.npy (float32)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="with --full: bounded CPU baseline sample (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0,
-                    help="CPU baseline threads (0 = every CPU in this process's affinity mask)")
+                    help="with --full: CPU baseline threads (0 = every CPU in this process's affinity mask)")
     ap.add_argument("--reference-steps", type=int, default=3,
-                    help="after the FAST legs, time this many steps of the same workload in REFERENCE arithmetic "
+                    help="with --full: after the FAST legs, time this many steps of the same workload in REFERENCE arithmetic "
                          "(the bit-exact path; rank 0, configs 3/4; 0 = skip)")
     ap.add_argument("--extra-legs", default="4,5,dh7,collide",
-                    help="with the default config 3: also time these BASELINE lines in the same run and print them "
+                    help="with --full and the default config 3: also time these BASELINE lines in the same run and print them "
                          "under 'legs' (4 = config 4's 8192 targets per GPU, 5 = config 5, dh7 = the DH arm, "
                          "collide = config 3 with the reference's collider boxes)")
-    ap.add_argument("--extra-steps", type=int, default=2, help="timed steps per extra leg (0 = no extra legs)")
+    ap.add_argument("--extra-steps", type=int, default=2,
+                    help="with --full: timed steps per extra leg (0 = no extra legs)")
     ap.add_argument("--extra-warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=100,
-                    help="with config 3: median wall time of this many consecutive visualiser calls (calculatePSO, "
+                    help="with --full and config 3: median wall time of this many consecutive visualiser calls (calculatePSO, "
                          "N = 16384, 15 iterations), FAST and REFERENCE (0 = skip)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="gloo: rehearse the N>1 path with ranks sharing the visible GPUs (not a measurement)")
@@ -268,7 +283,7 @@ def timed_leg(ctx, wl, Bl, P, I, steps, warmup, arith="fast", kernel="auto", col
     if gathered[0] != total:
         raise RuntimeError(f"all-gather returned {gathered[0]} rows, expected {total}")
     return {"elapsed": float(t[0]), "kern_ms": float(t[1]), "solver": solver, "D": D, "total": total,
-            "gathered_rows": gathered[0],
+            "gathered_rows": gathered[0], "rows": res,
             "targets": targets, "first": first, "finite": bool(np.isfinite(res).all()),
             "mean_fitness": float(res[:, D].mean()), "mean_residual": float(res[:, D + 1].mean())}
 
@@ -312,6 +327,28 @@ def frame_latency(ikpso, torch, np, arith: str, frames: int = 100):
             "p90_ms": round(float(np.percentile(t, 90)), 4), "frames": frames, "warmup": 1,
             "particle_updates_per_s": P * ikpso.MAIN_PSO.iterations / (float(np.median(t)) / 1e3),
             "residual_after": round(float(scene.check_distance()), 5)}
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory: str, rows, D: int) -> None:
+    """What the last timed step handed its caller -- the gathered (total, D + 2)
+    host rows: each swarm's answer angles, its fitness and its residual -- as
+    float32 .npy files.  Above 64 MB in all, a fixed seeded sample of the swarms
+    (ascending), whose indices go to swarm_index.npy."""
+    import numpy as np
+
+    rows = np.array(rows, dtype=np.float32)  # a copy: the pinned buffer goes with the leg
+    keep = DUMP_LIMIT_BYTES // (8 + rows.shape[1] * 4)
+    os.makedirs(directory, exist_ok=True)
+    if rows.shape[0] > keep:
+        index = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+        rows = rows[index]
+        np.save(os.path.join(directory, "swarm_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(directory, "angles.npy"), np.ascontiguousarray(rows[:, :D]))
+    np.save(os.path.join(directory, "fitness.npy"), np.ascontiguousarray(rows[:, D]))
+    np.save(os.path.join(directory, "residual.npy"), np.ascontiguousarray(rows[:, D + 1]))
 
 
 def rank_records(dist, torch, world: int, rank: int, local: int, backend: str):
@@ -512,7 +549,7 @@ def main():
     # the bounded CPU baseline runs before the GPU legs, on rank 0 at every N (north_star: the CPU path
     # "alongside" at 1, 2, 4 and 8 GPUs); the other ranks wait for it at a barrier
     cpu = None
-    if rank == 0 and args.cpu_seconds > 0 and cfg in (3, 5, "dh7", "dh7-nofold", "dh7-locked"):
+    if args.full and rank == 0 and args.cpu_seconds > 0 and cfg in (3, 5, "dh7", "dh7-nofold", "dh7-locked"):
         cpu = cpu_baseline(args.cpu_seconds, args.cpu_threads, dh=wl if isinstance(cfg, str) else None)
         if cfg == 5:  # the config-5 figure is this line's baseline
             cpu = dict(cpu, value=cpu["config5"]["value"], sample=cpu["config5"]["sample"])
@@ -536,9 +573,11 @@ def main():
     targets, first = main_leg["targets"], main_leg["first"]
     ups_step = total * P * I
     value = ups_step * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, main_leg["rows"], D)
 
     single_ms = single_p10 = None
-    if rank == 0 and cfg != 5 and colliders is None:
+    if args.full and rank == 0 and cfg != 5 and colliders is None:
         s2 = ikpso.BatchSolver(wl.chain, P, pso=ikpso.PSOConfig(0.5, 0.5, 1.25, I), fit=wl.fit, arith=args.arith,
                                axis_mask=wl.axis_mask, fold=wl.fold)
         s2.seed(1)
@@ -564,7 +603,7 @@ def main():
 
     # the REFERENCE-arithmetic (bit-identical to the oracle) throughput of the same workload, driver-measured
     reference_arith = None
-    if rank == 0 and args.arith == "fast" and args.reference_steps > 0 and cfg in (3, 4) and colliders is None:
+    if args.full and rank == 0 and args.arith == "fast" and args.reference_steps > 0 and cfg in (3, 4) and colliders is None:
         sr = ikpso.BatchSolver(wl.chain, P, pso=ikpso.PSOConfig(0.5, 0.5, 1.25, I), fit=wl.fit, arith="reference",
                                kernel=args.kernel)
         sr.seed(Bl, seed_base=0, first_swarm=first)
@@ -597,14 +636,14 @@ def main():
 
     # the visualiser's own per-frame call (N = 16384, 15 iterations), both arithmetic modes
     frame = None
-    if rank == 0 and cfg == 3 and args.frames > 0 and colliders is None:
+    if args.full and rank == 0 and cfg == 3 and args.frames > 0 and colliders is None:
         frame = {a: frame_latency(ikpso, torch, np, a, args.frames) for a in ("fast", "reference")}
 
     lib_id = ikpso.build_id()
     # the other BASELINE lines, same run and timing rules (every rank): config 4's per-GPU shard, config 5 at
     # its named size, the DH arm -- after the headline legs so the GPU stays busy to the end of the run
     legs = {}
-    if cfg == 3 and args.extra_steps > 0 and colliders is None:
+    if args.full and cfg == 3 and args.extra_steps > 0 and colliders is None:
         for name in args.extra_legs.split(","):
             name = name.strip()
             if name == "collide":
@@ -663,6 +702,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": "weak",

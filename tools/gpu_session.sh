@@ -36,6 +36,8 @@ step() {  # step NAME SECONDS CMD...
   local rc=$?; echo "   rc=$rc"; tail -4 "gpurun_out/$name.log" | cut -c1-400
   return $rc
 }
+# the bench and rocprof stages record the whole line (every leg, the CPU baseline, ...): bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for s in "$@"; do
   case $s in
     tests)
@@ -46,10 +48,10 @@ for s in "$@"; do
     bench) step bench 600 python bench.py ${BENCH_ARGS:-} || exit 4; tail -1 gpurun_out/bench.log > gpurun_out/bench.json ;;
     bench:*)
       c=${s#bench:}
-      step "bench_$c" 600 python bench.py --config "$c" --steps 3 --warmup 1 --cpu-seconds 4 || exit 4
+      step "bench_$c" 600 python bench.py --full --config "$c" --steps 3 --warmup 1 --cpu-seconds 4 || exit 4
       tail -1 "gpurun_out/bench_$c.log" > "gpurun_out/bench_$c.json" ;;
     gloo2)
-      step gloo2 600 python bench.py --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --cpu-seconds 4 || exit 4
+      step gloo2 600 python bench.py --full --gpus 2 --dist-backend gloo --steps 3 --warmup 1 --cpu-seconds 4 || exit 4
       grep '^{' gpurun_out/gloo2.log | tail -1 > gpurun_out/bench_gloo2.json ;;
     rocprof)
       step rocprof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_default -o run --output-format csv -- \
