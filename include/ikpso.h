@@ -235,6 +235,29 @@ ikpso_status ikpso_solve_batch(ikpso_solver* solver, const float* targets, const
                                int64_t num_swarms, int32_t iterations, float* out_angles, float* out_fitness,
                                float* out_residual, void* stream);
 
+/* Solve to a fitness tolerance: solve_batch with a per-swarm early stop (added
+ * after ABI 5; detect by symbol).  The arguments are solve_batch's, plus
+ *   stop_fitness   threshold on the FITNESS, the quantity PSO minimises (the
+ *                  weighted distance, angle and optional terms) -- not on the
+ *                  residual.  Negative: never stop.  NaN: IKPSO_ERR_INVALID_ARG.
+ *   out_iterations device, [B] or NULL: iterations each swarm ran.
+ * Swarm b stops after the first iteration n >= 0 at which its global-best
+ * fitness is <= stop_fitness (n = 0: the initial global best, before any PSO
+ * iteration, already meets it); otherwise it runs max_iterations.  A stopped
+ * swarm's outputs and generator states are those of solve_batch with
+ * iterations = n, bit for bit: a particle has drawn D + 3 D n values, no more.
+ * Stream-ordered; does not synchronise.  Runs the resident kernel (where a
+ * stopped swarm's workgroup ends and its CU takes the next swarm) or the
+ * streaming kernels (a stopped swarm's chunks idle through the remaining
+ * launches).  The cooperative kernels have no stop: a solver that AUTO routed to
+ * them runs the streaming kernels here, a resident solver never takes the
+ * few-swarm cooperative route, and a solver created with IKPSO_KERNEL_COOP gets
+ * IKPSO_ERR_UNSUPPORTED. */
+ikpso_status ikpso_solve_batch_until(ikpso_solver* solver, const float* targets, const float* start_pose,
+                                     int64_t num_swarms, int32_t max_iterations, float stop_fitness,
+                                     float* out_angles, float* out_fitness, float* out_residual,
+                                     int32_t* out_iterations, void* stream);
+
 /* Settle the last solve_batch (ABI >= 3).  After a cooperative-family solve:
  * wait for it and, if a group gave up (the GPU shared with other work), restore
  * the generator states from the snapshot taken before the launch and re-run the
@@ -277,7 +300,8 @@ int ikpso_solver_effectors(const ikpso_solver* solver);
 int ikpso_solver_collider_count(const ikpso_solver* solver);
 /* Name of the kernel variant the solver dispatches to (family / topology); after a
  * solve_batch that AUTO routed to the cooperative latency variant (a few swarms),
- * that variant's name until the next solve. */
+ * that variant's name until the next solve; after a solve_batch_until that ran the
+ * streaming kernels for a cooperative solver, theirs. */
 const char* ikpso_solver_kernel_name(const ikpso_solver* solver);
 
 int ikpso_abi_version(void);

@@ -689,6 +689,7 @@ void carve_stream(StreamIO& io, void* ws, int64_t B, int P, int D, bool own_stat
     io.gkey = cv.take<uint32_t>((size_t)2 * B);
     io.gidx = cv.take<int32_t>((size_t)2 * B);
     io.gvec = cv.take<float>((size_t)2 * B * D);
+    io.iters = cv.take<int32_t>((size_t)B);
     io.num_swarms = B;
     io.P = P;
     io.C = C;
@@ -821,6 +822,8 @@ struct ikpso_solver {
     std::string kname;     // kernel family / topology, for ikpso_solver_kernel_name
     std::string kname_latency;  // the cooperative latency variant AUTO may pick per call
     bool last_latency = false;  // the last solve_batch ran the latency variant
+    std::string kname_stream;   // the streaming kernels solve_batch_until runs for an AUTO cooperative solver
+    bool last_stream = false;   // the last solve ran them
     void* ws = nullptr;    // streaming / cooperative workspace
     size_t ws_bytes = 0;
     int P = 0;
@@ -871,7 +874,8 @@ ikpso_status grow(void** buf, size_t* have, size_t need)
 // co-residency requirement).
 ikpso_status solve_streaming(ikpso_solver* s, void** ws, size_t* ws_bytes, const float* targets,
                              const float* start_pose, int64_t num_swarms, int32_t iterations, float* out_angles,
-                             float* out_fitness, float* out_residual, hipStream_t hs)
+                             float* out_fitness, float* out_residual, hipStream_t hs, uint32_t stop_key = 0,
+                             int32_t* out_iterations = nullptr)
 {
     const ChainHost& ch = s->solve_chain();
     const int D = ch.kernel_dims();
@@ -886,7 +890,30 @@ ikpso_status solve_streaming(ikpso_solver* s, void** ws, size_t* ws_bytes, const
     io.out_angles = out_angles;
     io.out_fitness = out_fitness;
     io.out_residual = out_residual;
+    io.stop_key = stop_key;
+    io.out_iterations = out_iterations;
     IKPSO_HIP(launch_stream(ch, s->mode, io, iterations, hs));
+    return IKPSO_OK;
+}
+
+// The batch on the resident kernel: one launch, one workgroup per swarm.
+ikpso_status solve_resident(ikpso_solver* s, const float* targets, const float* start_pose, int64_t num_swarms,
+                            int32_t iterations, float* out_angles, float* out_fitness, float* out_residual,
+                            hipStream_t hs, uint32_t stop_key = 0, int32_t* out_iterations = nullptr)
+{
+    SwarmIO io{};
+    io.targets = targets;
+    io.start_pose = start_pose;
+    io.rng = s->rng;
+    io.out_angles = out_angles;
+    io.out_fitness = out_fitness;
+    io.out_residual = out_residual;
+    io.P = s->P;
+    io.iterations = iterations;
+    io.num_swarms = num_swarms;
+    io.stop_key = stop_key;
+    io.out_iterations = out_iterations;
+    IKPSO_HIP(launch_resident(s->solve_chain(), s->mode, io, hs));
     return IKPSO_OK;
 }
 
@@ -1165,6 +1192,7 @@ ikpso_status ikpso_solver_create(const ikpso_solver_desc* desc, ikpso_solver** o
     s->family = pick_kernel(sch, s->mode, s->P, desc->kernel);
     s->requested = desc->kernel;
     if (s->family >= 0) s->kname = kernel_name(sch, s->family);
+    if (s->family >= 0) s->kname_stream = kernel_name(sch, IKPSO_KERNEL_STREAMING);
     if (s->family >= 0)
         s->kname_latency = kernel_name(sch, IKPSO_KERNEL_COOP) +
                            (coop_latency_split(sch) ? " (latency variant, generator waves)" : " (latency variant)");
@@ -1234,20 +1262,10 @@ ikpso_status ikpso_solve_batch(ikpso_solver* s, const float* targets, const floa
     const bool latency_coop = s->family == IKPSO_KERNEL_RESIDENT && s->requested == IKPSO_KERNEL_AUTO &&
                               prefer_latency_coop(ch, s->mode, s->P, num_swarms);
     s->last_latency = latency_coop;
-    if (s->family == IKPSO_KERNEL_RESIDENT && !latency_coop) {
-        SwarmIO io{};
-        io.targets = targets;
-        io.start_pose = start_pose;
-        io.rng = s->rng;
-        io.out_angles = out_angles;
-        io.out_fitness = out_fitness;
-        io.out_residual = out_residual;
-        io.P = s->P;
-        io.iterations = iterations;
-        io.num_swarms = num_swarms;
-        IKPSO_HIP(launch_resident(ch, s->mode, io, hs));
-        return IKPSO_OK;
-    }
+    s->last_stream = false;
+    if (s->family == IKPSO_KERNEL_RESIDENT && !latency_coop)
+        return solve_resident(s, targets, start_pose, num_swarms, iterations, out_angles, out_fitness, out_residual,
+                              hs);
     const int D = ch.kernel_dims();
     if (s->family == IKPSO_KERNEL_COOP || latency_coop) {
         int G, NG, T;
@@ -1324,6 +1342,41 @@ ikpso_status ikpso_solve_batch(ikpso_solver* s, const float* targets, const floa
     return solve_streaming(s, &s->ws, &s->ws_bytes, targets, start_pose, num_swarms, iterations, out_angles,
                            out_fitness, out_residual, hs);
 }
+
+// The cooperative kernels draw the next iteration's first dimensions inside the
+// exchange that would decide whether that iteration runs, so they have no stop: a
+// solver AUTO routed to them runs the streaming kernels here, and a resident solver
+// never takes the few-swarm cooperative latency route.
+ikpso_status ikpso_solve_batch_until(ikpso_solver* s, const float* targets, const float* start_pose,
+                                     int64_t num_swarms, int32_t max_iterations, float stop_fitness,
+                                     float* out_angles, float* out_fitness, float* out_residual,
+                                     int32_t* out_iterations, void* stream)
+{
+    if (!s || num_swarms < 0 || max_iterations < 0 || stop_fitness != stop_fitness) return IKPSO_ERR_INVALID_ARG;
+    if (num_swarms == 0) return IKPSO_OK;
+    if (!out_angles) return IKPSO_ERR_INVALID_ARG;
+    if (num_swarms > s->capacity || !s->rng) return IKPSO_ERR_INVALID_ARG;  // seed first
+    if (num_swarms > 0x7fffffff) return IKPSO_ERR_INVALID_ARG;
+    if (s->requested == IKPSO_KERNEL_COOP) return IKPSO_ERR_UNSUPPORTED;
+    IKPSO_HIP(take_pending_error());
+    const hipStream_t hs = (hipStream_t)stream;
+    if (s->pending.active) {  // the previous cooperative solve was not synced: settle it first
+        const ikpso_status st = ikpso_solver_sync(s);
+        if (st != IKPSO_OK) return st;
+    }
+    const uint32_t stop_key = stop_fitness < 0.0f ? 0u : ordered_key_host(stop_fitness);  // negative: never stop
+    s->last_latency = false;
+    s->last_stream = s->family != IKPSO_KERNEL_RESIDENT;
+    if (!s->last_stream)
+        return solve_resident(s, targets, start_pose, num_swarms, max_iterations, out_angles, out_fitness,
+                              out_residual, hs, stop_key, out_iterations);
+    return solve_streaming(s, &s->ws, &s->ws_bytes, targets, start_pose, num_swarms, max_iterations, out_angles,
+                           out_fitness, out_residual, hs, stop_key, out_iterations);
+}
+
+// ordered_key_host / key_to_float, for the tests (not part of the declared ABI)
+uint32_t ikpso_debug_ordered_key(float f) { return ordered_key_host(f); }
+float ikpso_debug_key_to_float(uint32_t k) { return key_to_float_host(k); }
 
 ikpso_status ikpso_solver_sync(ikpso_solver* s)
 {
@@ -1406,7 +1459,7 @@ int ikpso_solver_effectors(const ikpso_solver* s) { return s ? s->chain.E : 0; }
 int ikpso_solver_collider_count(const ikpso_solver* s) { return s ? s->chain.num_coll : 0; }
 const char* ikpso_solver_kernel_name(const ikpso_solver* s)
 {
-    return s ? (s->last_latency ? s->kname_latency : s->kname).c_str() : "";
+    return s ? (s->last_stream ? s->kname_stream : s->last_latency ? s->kname_latency : s->kname).c_str() : "";
 }
 
 }  // extern "C"

@@ -232,6 +232,23 @@ ChainConsts<J> make_consts(const ChainHost& h)
     return c;
 }
 
+// Host twins of ordered_key / key_to_float (ikpso_device.h): the order-preserving map
+// of an fp32 value to uint32, -0 canonicalised to +0 by the same `f + 0.0f`.
+inline uint32_t ordered_key_host(float f)
+{
+    const float c = f + 0.0f;  // -0 -> +0 (IEEE: not folded away without fast-math)
+    uint32_t u;
+    memcpy(&u, &c, 4);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+inline float key_to_float_host(uint32_t k)
+{
+    const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
 hipError_t launch_init_generators(ikpso_rng_state* st, int64_t count, uint64_t seed_base, hipStream_t stream);
 hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream);
 hipError_t launch_stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t stream);

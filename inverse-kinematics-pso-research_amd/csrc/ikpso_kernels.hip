@@ -208,7 +208,8 @@ size_t stream_workspace_bytes(int64_t B, int P, int D, bool with_state)
     n += sizeof(float) * 2 * B * C * D;                   // partial vectors
     n += (sizeof(uint32_t) + sizeof(int32_t)) * 2 * B;      // global best key/idx
     n += sizeof(float) * 2 * B * D;                       // global best vector
-    return n + 8 * 256;                                   // alignment slack
+    n += sizeof(int32_t) * B;                             // iteration counts (solve_batch_until)
+    return n + 9 * 256;                                   // alignment slack
 }
 
 

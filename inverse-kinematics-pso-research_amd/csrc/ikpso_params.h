@@ -97,6 +97,12 @@ struct SwarmIO {
     // every swarm is started in the launch's first round (the hosts pass it for
     // one swarm: a group that gives up never loads its later swarms).
     ikpso_rng_state* rng_snap;
+    // Resident kernel only (ikpso_solve_batch_until): the swarm stops once its
+    // global-best key is <= stop_key, the threshold as ordered_key maps it
+    // (ordered_key_host, ikpso_kernels.h).  0 disables the stop: no finite
+    // fitness has key 0.
+    uint32_t stop_key;
+    int32_t* out_iterations;  // [B] iterations each swarm ran, or null
 };
 
 // Streaming (state-in-HBM) kernels: one launch per PSO iteration over every
@@ -126,7 +132,11 @@ struct StreamIO {
     int32_t P;
     int32_t C;                  // chunks per swarm
     int32_t t;                  // launch index (see above)
-    int32_t pad_;
+    // ikpso_solve_batch_until: a swarm whose global best as of launch t-1 has a key
+    // <= stop_key is frozen from launch t on (0 disables the stop, see SwarmIO)
+    uint32_t stop_key;
+    int32_t* iters;             // [B] iterations a frozen swarm ran, -1 while it runs (set by the init launch)
+    int32_t* out_iterations;    // [B] or null: written by the finalize launch
 };
 
 }  // namespace ikpso

@@ -378,7 +378,10 @@ __device__ __forceinline__ void init_particle(const ChainConsts<Topo::J>& cc, co
 // The kernel body over its LDS: the per-swarm uniforms `sh` and the local-best
 // positions s_pb[d * BLOCK + lane] (read once per iteration by the update,
 // written on improvement; consecutive lanes hit consecutive banks).
-template <class Topo, int MODE, int TERMS>
+// STOP: the instantiation ikpso_solve_batch_until runs (the early stop below).  A template
+// parameter, not a run-time test in the one kernel: with the test in the plain kernel's loop
+// the compiler scheduled the headline iteration differently and it ran 7 % slower (DESIGN).
+template <class Topo, int MODE, int TERMS, bool STOP>
 __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& cc, const SwarmIO& io,
                                                     SwarmShared<Topo>& sh, float* const s_pb)
 {
@@ -412,7 +415,12 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
     __syncthreads();
 
     const PsoCoef coef = pso_coef(cc);
-    for (int it = 0; it < io.iterations; ++it) {
+    // STOP (ikpso_solve_batch_until): the swarm stops once its global best meets the
+    // threshold (io.stop_key; 0 = never).  Tested after the first copy and after each
+    // iteration's update; gkey is uniform, so the whole workgroup leaves together and what
+    // follows is what a run of `it` iterations does.
+    int it = 0;
+    for (; it < io.iterations && (!STOP || gkey > io.stop_key); ++it) {
         compiler_fence();
         if constexpr ((TERMS & kTermColliders) && IKPSO_COLLIDE_RELOAD) {
             // the chain constants re-read from the kernarg segment every iteration (kernarg_cc)
@@ -435,6 +443,9 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
     compiler_fence();
     store_angles<Topo, TERMS>(cc, io.out_angles, b, tid, tid < D ? sh.g[tid] : 0.0f);
     if (tid == 0 && io.out_fitness) io.out_fitness[b] = key_to_float(gkey);
+    if constexpr (STOP) {
+        if (tid == 0 && io.out_iterations) io.out_iterations[b] = it;
+    }
     if (io.out_residual && tid < 64) {
         float g[D];
 #pragma unroll
@@ -475,7 +486,7 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
 template <class Topo>
 constexpr int kResidentMinWaves = Topo::kDH ? 8 : 1;
 
-template <class Topo, int MODE, int TERMS>
+template <class Topo, int MODE, int TERMS, bool STOP = false>
 __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWaves<Topo>)
     k_swarm_resident(const ChainConsts<Topo::J> cc, const SwarmIO io)
 {
@@ -486,10 +497,10 @@ __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWa
         // LDS object (an illegal flat-to-LDS check)
         __shared__ SwarmShared<Topo> sh;
         __shared__ float s_pb[NPB];
-        swarm_resident_body<Topo, MODE, TERMS>(cc, io, sh, s_pb);
+        swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, sh, s_pb);
     } else {
         __shared__ SwarmLds<Topo, NPB> lds;  // uniforms below 64 KiB (SwarmLds)
-        swarm_resident_body<Topo, MODE, TERMS>(cc, io, lds.sh, lds.pb);
+        swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, lds.sh, lds.pb);
     }
 }
 
@@ -533,6 +544,19 @@ __global__ void __launch_bounds__(256) k_evaluate(const ChainConsts<Topo::J> cc,
 }
 
 // --------------------------------------------------------------- dispatch
+// One resident build: its plain kernel, or for ikpso_solve_batch_until (a threshold or an
+// iteration-count output) its stopping twin.
+template <class Topo, int MODE, int TERMS>
+inline hipError_t launch_resident_build(const ChainConsts<Topo::J>& cc, const SwarmIO& io, dim3 grid, dim3 threads,
+                                        hipStream_t stream)
+{
+    if (io.stop_key != 0 || io.out_iterations)
+        hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, TERMS, true>), grid, threads, 0, stream, cc, io);
+    else
+        hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, TERMS, false>), grid, threads, 0, stream, cc, io);
+    return hipGetLastError();
+}
+
 template <class Topo, int MODE>
 inline hipError_t run_resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
 {
@@ -549,59 +573,43 @@ inline hipError_t run_resident(const ChainHost& ch, const SwarmIO& io, int block
     const int terms = term_set(ch);
     hipError_t err = hipSuccess;
     if (dh_terms<Topo>(terms, &err, [&](auto t) {
-            hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, decltype(t)::value | kTermRev>), grid, threads, 0, stream,
-                               cc, io);
-            return hipGetLastError();
+            return launch_resident_build<Topo, MODE, decltype(t)::value | kTermRev>(cc, io, grid, threads, stream);
         }))
         return err;
     if constexpr (!Topo::kGeneric && !Topo::kDH && MODE == IKPSO_ARITH_FAST) {
         if constexpr (std::is_same_v<Topo, TopoRef7>) {  // the reference scene's [0, 2pi] limits
-            if (terms == kTermUniformBounds && ch.unit_rev_bounds) {
-                hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, kTermUniformBounds | kFastRev | kFastUnitBounds>),
-                                   grid, threads, 0, stream, cc, io);
-                return hipGetLastError();
-            }
+            if (terms == kTermUniformBounds && ch.unit_rev_bounds)
+                return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev | kFastUnitBounds>(
+                    cc, io, grid, threads, stream);
         }
-        if (terms == kTermUniformBounds) {
-            hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, kTermUniformBounds | kFastRev>), grid, threads, 0, stream,
-                               cc, io);
-            return hipGetLastError();
-        }
+        if (terms == kTermUniformBounds)
+            return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev>(cc, io, grid, threads, stream);
         if constexpr (std::is_same_v<Topo, TopoRef7> && IKPSO_COLLIDE_UNIFORM) {
             // the reference scene with colliders (the bench's collide leg): no runtime term tests, the clamp
             // bounds uniform (the separating-axis builds: colliders that are rotations, angles in the unit's range)
-            if (terms == (kTermUniformBounds | kTermColliders) && ch.num_coll > 0 && ch.coll_obb && !ch.poly_trig) {
-                hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, kTermUniformBounds | kTermColliders>), grid, threads, 0,
-                                   stream, cc, io);
-                return hipGetLastError();
-            }
+            if (terms == (kTermUniformBounds | kTermColliders) && ch.num_coll > 0 && ch.coll_obb && !ch.poly_trig)
+                return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermColliders>(cc, io, grid, threads,
+                                                                                              stream);
         }
         if constexpr (std::is_same_v<Topo, TopoSerialTip<20>>) {  // BASELINE config 5's symmetric soft limits
-            if (terms == (kTermUniformBounds | kTermPenalty) && ch.sym_penalty) {
-                hipLaunchKernelGGL(
-                    (k_swarm_resident<Topo, MODE, kTermUniformBounds | kTermPenalty | kFastRev | kFastSymPenalty>),
-                    grid, threads, 0, stream, cc, io);
-                return hipGetLastError();
-            }
+            if (terms == (kTermUniformBounds | kTermPenalty) && ch.sym_penalty)
+                return launch_resident_build<Topo, MODE,
+                                             kTermUniformBounds | kTermPenalty | kFastRev | kFastSymPenalty>(
+                    cc, io, grid, threads, stream);
         }
-        if (terms == (kTermUniformBounds | kTermPenalty)) {
-            hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, kTermUniformBounds | kTermPenalty | kFastRev>), grid,
-                               threads, 0, stream, cc, io);
-            return hipGetLastError();
-        }
+        if (terms == (kTermUniformBounds | kTermPenalty))
+            return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermPenalty | kFastRev>(cc, io, grid,
+                                                                                                   threads, stream);
     }
     // REFERENCE on the reference scene (the bit-exact path the bench's reference_arith leg and the
     // recorded-trajectory replay run): no runtime term tests, the median clamp for ordered bounds
     if constexpr (std::is_same_v<Topo, TopoRef7> && MODE == IKPSO_ARITH_REFERENCE && IKPSO_REF_UNIFORM_BUILD) {
-        if (terms == kTermUniformBounds && ch.ordered_bounds) {
-            hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, kTermUniformBounds>), grid, threads, 0, stream, cc, io);
-            return hipGetLastError();
-        }
+        if (terms == kTermUniformBounds && ch.ordered_bounds)
+            return launch_resident_build<Topo, MODE, kTermUniformBounds>(cc, io, grid, threads, stream);
     }
     (void)terms;
     return with_runtime_terms<Topo>(ch, [&](auto t) {
-        hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, decltype(t)::value>), grid, threads, 0, stream, cc, io);
-        return hipGetLastError();
+        return launch_resident_build<Topo, MODE, decltype(t)::value>(cc, io, grid, threads, stream);
     });
 }
 

@@ -84,6 +84,26 @@ __device__ __forceinline__ void stream_publish_chunk(const StreamIO& io, int64_t
     }
 }
 
+// A frozen swarm (ikpso_solve_batch_until: its global best met the threshold in an
+// earlier launch): the chunk takes no draws and writes no state; it carries its partial
+// record from slot (t-1)&1 to slot t&1, the only slot the next launch reads, and chunk 0
+// records the iteration count the first time.  Every later launch resolves the same
+// global best and freezes the swarm again.
+template <class Topo>
+__device__ __forceinline__ void stream_carry_chunk(const StreamIO& io, int64_t b, int c)
+{
+    constexpr int D = Topo::D;
+    const int prev = (io.t - 1) & 1, cur = io.t & 1;
+    const int64_t from = ((int64_t)prev * io.num_swarms + b) * io.C + c;
+    const int64_t to = ((int64_t)cur * io.num_swarms + b) * io.C + c;
+    if (threadIdx.x == 0) {
+        io.pkey[to] = io.pkey[from];
+        io.pidx[to] = io.pidx[from];
+        if (c == 0 && io.iters[b] < 0) io.iters[b] = io.t - 1;
+    }
+    for (int d = threadIdx.x; d < D; d += blockDim.x) io.pvec[to * D + d] = io.pvec[from * D + d];
+}
+
 template <class Topo, int MODE, int TERMS>
 __global__ void __launch_bounds__(kStreamChunk) k_stream_init(const ChainConsts<Topo::J> cc, const StreamIO io)
 {
@@ -125,7 +145,10 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_init(const ChainConsts<
         io.rng[5 * n + k] = rng.v4;
     }
     stream_publish_chunk<Topo>(io, b, c, sh, active ? ordered_key(pbf) : 0xFFFFFFFFu, pl);
-    if (c == 0 && threadIdx.x == 0) io.gkey[(int64_t)(io.t & 1) * io.num_swarms + b] = 0xFFFFFFFFu;
+    if (c == 0 && threadIdx.x == 0) {
+        io.gkey[(int64_t)(io.t & 1) * io.num_swarms + b] = 0xFFFFFFFFu;
+        io.iters[b] = -1;  // running (stream_carry_chunk)
+    }
 }
 
 template <class Topo, int MODE, int TERMS>
@@ -140,8 +163,12 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_step(const ChainConsts<
     const int64_t P = io.P;
     __shared__ SwarmShared<Topo> sh;
     stage_swarm_inputs<Topo>(cc, io.targets, io.start_pose, b, sh);
-    stream_resolve_gbest<Topo>(io, b, c, sh);
+    const uint32_t gkey = stream_resolve_gbest<Topo>(io, b, c, sh);
     __syncthreads();
+    if (gkey <= io.stop_key) {  // uniform, and the same in every chunk of the swarm
+        stream_carry_chunk<Topo>(io, b, c);
+        return;
+    }
 
     const Planes pl(io.state + b * 3 * D * P, D, (int)P, i);
     float pbf = 0.0f;
@@ -278,6 +305,8 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_finalize(const ChainCon
         // Coordinates result (updateGlobalBestCoordsKernel) + fitness + residual
         for (int d = threadIdx.x; d < D; d += blockDim.x) store_angles<Topo>(cc, io.out_angles, b, d, sh.g[d]);
         if (threadIdx.x == 0 && io.out_fitness) io.out_fitness[b] = key_to_float(gkey);
+        if (threadIdx.x == 0 && io.out_iterations)  // this is launch max_iterations + 1
+            io.out_iterations[b] = io.iters[b] < 0 ? io.t - 1 : io.iters[b];
         if (io.out_residual && threadIdx.x < 64) {
             float g[D];
 #pragma unroll

@@ -279,6 +279,42 @@ class BatchSolver:
             _abi.check(self._lib.ikpso_solver_sync(self._h), "ikpso_solver_sync")
         return angles, fitness, res
 
+    def solve_until(self, targets=None, start_pose=None, max_iterations: Optional[int] = None,
+                    stop_fitness: Optional[float] = None, num_swarms: Optional[int] = None, residual: bool = True,
+                    stream=None):
+        """solve() with a per-swarm early stop (ikpso_solve_batch_until): swarm b stops after the
+        first iteration n >= 0 at which its global-best fitness is <= stop_fitness, else it runs
+        max_iterations (None: the solver's PSOConfig.iterations).  stop_fitness tests the fitness,
+        not the residual; None takes the solver's FitnessConfig.error_threshold, a negative value
+        never stops.  Returns (angles [B, D], fitness [B], residual [B] or None, iterations [B]
+        int32) device tensors; a stopped swarm's answers and generator states are those of
+        solve(iterations=n), bit for bit.  Runs the resident or the streaming kernels; a
+        kernel="coop" solver raises (unsupported configuration).  Stream-ordered, asynchronous."""
+        torch = _torch()
+        if num_swarms is None:
+            if targets is None:
+                raise ValueError("num_swarms is required when targets is None")
+            num_swarms = int(targets.shape[0])
+        B = int(num_swarms)
+        it = self.pso.iterations if max_iterations is None else int(max_iterations)
+        stop = self.fit.error_threshold if stop_fitness is None else float(stop_fitness)
+        if targets is not None and tuple(targets.shape) != (B, self.effectors, 3):
+            raise ValueError(f"targets must be [{B}, {self.effectors}, 3]")
+        if start_pose is not None and tuple(start_pose.shape) != (B, self.dof):
+            raise ValueError(f"start_pose must be [{B}, {self.dof}]")
+        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        angles = torch.empty((B, self.dof), dtype=torch.float32, device=dev)
+        fitness = torch.empty((B,), dtype=torch.float32, device=dev)
+        res = torch.empty((B,), dtype=torch.float32, device=dev) if residual else None
+        iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        for t, name in ((targets, "targets"), (start_pose, "start_pose")):
+            self._check_tensor(t, name, dev)
+        _abi.check(self._lib.ikpso_solve_batch_until(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, it, stop,
+                                                     _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
+                                                     _dev_ptr(iters), _stream_handle(stream)),
+                   "ikpso_solve_batch_until")
+        return angles, fitness, res, iters
+
     def sync(self) -> None:
         """ikpso_solver_sync: settle the last solve (see solve(sync=...))."""
         _abi.check(self._lib.ikpso_solver_sync(self._h), "ikpso_solver_sync")
