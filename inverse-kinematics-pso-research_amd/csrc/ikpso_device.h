@@ -1479,6 +1479,28 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t x)
     return min(min(r0, r1), min(r2, r3));
 }
 
+// The same with the four row minima combined by s_min_u32.  Left to the compiler they meet in a
+// v_min3_u32, which takes one scalar operand: two v_mov feed it, and the minimum -- and whatever
+// is compared with it from one iteration to the next -- stays in a vector register.
+__device__ __forceinline__ uint32_t scalar_min_u32(uint32_t a, uint32_t b)
+{
+    uint32_t r;
+    asm("s_min_u32 %0, %1, %2" : "=s"(r) : "s"(a), "s"(b) : "scc");
+    return r;
+}
+__device__ __forceinline__ uint32_t wave_min_u32_scalar(uint32_t x)
+{
+    x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)x, 0xB1, 0xF, 0xF, false));
+    x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)x, 0x4E, 0xF, 0xF, false));
+    x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)x, 0x141, 0xF, 0xF, false));
+    x = min(x, (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFF, (int)x, 0x140, 0xF, 0xF, false));
+    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)x, 0);
+    const uint32_t r1 = (uint32_t)__builtin_amdgcn_readlane((int)x, 16);
+    const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)x, 32);
+    const uint32_t r3 = (uint32_t)__builtin_amdgcn_readlane((int)x, 48);
+    return scalar_min_u32(scalar_min_u32(r0, r1), scalar_min_u32(r2, r3));
+}
+
 // Lowest lane whose key equals the (uniform) wave minimum.
 __device__ __forceinline__ int wave_first_lane_eq(uint32_t key, uint32_t wmin)
 {

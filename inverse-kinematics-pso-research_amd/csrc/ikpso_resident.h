@@ -67,6 +67,28 @@ __device__ __forceinline__ void progress_prio(int k)
     }
 }
 
+// A lane's column of the local bests, s_pb[d * BLOCK + lane].  A ds instruction's offset field
+// holds 16 bits, so with 1024 lanes dimensions 16 and up lie beyond the lane's own address, and
+// the compiler keeps one more address register per such dimension live across the iteration
+// (five on the reference scene).  SPLIT: those dimensions are addressed from a second lane index
+// kSplit dimensions up, which the compiler cannot fold back (upper_lane, taken once before the
+// iteration loop) -- one register for all of them.
+template <int BLOCK, bool SPLIT>
+struct PbLane {
+    static constexpr int kSplit = 65536 / (4 * BLOCK);
+    int lo, hi;
+    __device__ __forceinline__ static int upper_lane(int tid)
+    {
+        int h = tid + kSplit * BLOCK;
+        asm("" : "+v"(h));
+        return h;
+    }
+    __device__ __forceinline__ int at(int d) const
+    {
+        return SPLIT && d >= kSplit ? (d - kSplit) * BLOCK + hi : d * BLOCK + lo;
+    }
+};
+
 // One PSO iteration of one particle (lane `tid`) of a swarm whose local bests
 // sit in LDS as s_pb[d * BLOCK + lane] (shared by the resident and cooperative
 // kernels).  simulateParticlesKernel (src/kernel.cu:153-189) + calculateDistance
@@ -79,17 +101,17 @@ __device__ __forceinline__ void progress_prio(int k)
 // loaded one node ahead so their latency hides under the previous node.
 // simulateParticlesKernel for node k's A angles (draws r1, r2, r3 per
 // dimension, in dimension order; then the clamp).
-template <class Topo, int MODE, int TERMS, int BLOCK, class Rng>
+template <class Topo, int MODE, int TERMS, int BLOCK, bool SPLIT = false, class Rng>
 __device__ __forceinline__ void update_node(const ChainConsts<Topo::J>& cc, const SwarmShared<Topo>& sh,
-                                            const float* s_pb, int tid, int k, float (&x)[Topo::D],
-                                            float (&v)[Topo::D], const PsoCoef& coef, Rng& rng)
+                                            const float* s_pb, const PbLane<BLOCK, SPLIT>& pbl, int k,
+                                            float (&x)[Topo::D], float (&v)[Topo::D], const PsoCoef& coef, Rng& rng)
 {
     constexpr int A = Topo::A;
 #pragma unroll
     for (int ax = 0; ax < A; ++ax) {
         const int d = A * (k - 1) + ax;
         if (kMasked<Topo, TERMS> && !dim_free(cc, d)) continue;  // locked: stays at rest
-        pso_update<MODE>(x[d], v[d], s_pb[d * BLOCK + tid], sh.g[d], coef, rng);
+        pso_update<MODE>(x[d], v[d], s_pb[pbl.at(d)], sh.g[d], coef, rng);
         if constexpr (TERMS & kTermUniformBounds)
             x[d] = clamp_mode<MODE, true>(x[d], uniform_lo<TERMS>(cc), uniform_hi<TERMS>(cc));
         else
@@ -101,24 +123,24 @@ __device__ __forceinline__ void update_node(const ChainConsts<Topo::J>& cc, cons
 // node k+1's angles and evaluates their sines and cosines while it folds node k
 // into the FK, so the transcendental (or polynomial) latency of one node hides
 // under another node's FK.  The draws keep dimension order.
-template <class Topo, int MODE, int TERMS, int BLOCK, class Rng>
+template <class Topo, int MODE, int TERMS, int BLOCK, bool SPLIT = false, class Rng>
 __device__ __forceinline__ float swarm_step_ahead(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh,
-                                                  float* s_pb, int tid, float (&x)[Topo::D], float (&v)[Topo::D],
-                                                  const PsoCoef& coef, Rng& rng)
+                                                  float* s_pb, const PbLane<BLOCK, SPLIT>& pbl, float (&x)[Topo::D],
+                                                  float (&v)[Topo::D], const PsoCoef& coef, Rng& rng)
 {
     constexpr int J = Topo::J, A = Topo::A;
     constexpr int HW = kHwTrig<Topo, MODE, TERMS>;
     CandBuf<Topo, TERMS> cb;
     FitnessFor<Topo, MODE, TERMS> acc(cc, sh.dh, sh.soft, cb.v);
     progress_prio<J, kPrioLevels4Wave>(1);
-    update_node<Topo, MODE, TERMS, BLOCK>(cc, sh, s_pb, tid, 1, x, v, coef, rng);
+    update_node<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, 1, x, v, coef, rng);
     NodeTrig<A> cur = node_trig<HW, A>(x);
 #pragma unroll
     for (int k = 1; k <= J; ++k) {
         if (k > 1) progress_prio<J, kPrioLevels4Wave>(k);
         NodeTrig<A> nxt = cur;
         if (k < J) {
-            update_node<Topo, MODE, TERMS, BLOCK>(cc, sh, s_pb, tid, k + 1, x, v, coef, rng);
+            update_node<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, k + 1, x, v, coef, rng);
             nxt = node_trig<HW, A>(x + A * k);
         }
         float rest[A], tgt[3];
@@ -260,10 +282,11 @@ __device__ __forceinline__ const ChainConsts<J>& kernarg_cc()
 // Masked chains (kMasked builds): a locked dimension takes no draws and keeps
 // its rest value, as in the oracle's masked restatement.
 // KV: velocities held in LDS behind the local bests (kVelLds; the resident kernel)
-template <class Topo, int MODE, int TERMS, int BLOCK, int KV = 0, class Rng>
+// SPLIT: the pipelined step's local-best addressing (PbLane; the unrolled resident build)
+template <class Topo, int MODE, int TERMS, int BLOCK, int KV = 0, bool SPLIT = false, class Rng>
 __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh, float* s_pb,
                                            int tid, float (&x)[Topo::D], float (&v)[Topo::D], float& pbf,
-                                           const PsoCoef& coef, Rng& rng)
+                                           const PsoCoef& coef, Rng& rng, int tid_upper = 0)
 {
     constexpr int J = Topo::J, A = Topo::A, D = Topo::D;
     constexpr bool MASK = kMasked<Topo, TERMS>;
@@ -274,11 +297,12 @@ __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, Swarm
     // (not the collider builds: the pipelined step's extra live node spilled them)
     if constexpr (MODE == IKPSO_ARITH_FAST && Topo::D <= kTrigAheadMaxD && !(TERMS & kTermColliders)) {
         // updateLocalBests (src/kernel.cu:202-221): strict improvement
-        const float f = swarm_step_ahead<Topo, MODE, TERMS, BLOCK>(cc, sh, s_pb, tid, x, v, coef, rng);
+        const PbLane<BLOCK, SPLIT> pbl{tid, tid_upper};
+        const float f = swarm_step_ahead<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, x, v, coef, rng);
         if (f < pbf) {
             pbf = f;
 #pragma unroll
-            for (int d = 0; d < D; ++d) s_pb[d * BLOCK + tid] = x[d];
+            for (int d = 0; d < D; ++d) s_pb[pbl.at(d)] = x[d];
         }
         return;
     }
@@ -375,6 +399,51 @@ __device__ __forceinline__ void init_particle(const ChainConsts<Topo::J>& cc, co
 }
 
 // ------------------------------------------------------- resident swarm kernel
+// Builds whose iteration loop is unrolled by two (swarm_resident_body): the plain kernel of
+// the software-pipelined FAST step.  Not the stopping twin, whose loop tests the threshold
+// every iteration, and not the other steps, which are not changed.  Of the builds that share
+// the step only the reference scene's own (unit bounds) was timed, so only it is unrolled.
+#ifndef IKPSO_UNROLL_ITERATIONS
+#define IKPSO_UNROLL_ITERATIONS 1
+#endif
+template <class Topo, int MODE, int TERMS, bool STOP>
+constexpr bool kUnrollIterations = IKPSO_UNROLL_ITERATIONS && !STOP && MODE == IKPSO_ARITH_FAST &&
+                                   Topo::D <= kTrigAheadMaxD && !(TERMS & kTermColliders) &&
+                                   (TERMS & kTermUnitBounds) && !kTipBackward<Topo, MODE, TERMS>;
+
+// One iteration of the resident kernel: the step, then the swarm argmin and, on strict
+// improvement, the global-best copy.  par: the argmin's LDS buffer, (it + 1) & 1.  TUNED: the
+// unrolled build (kUnrollIterations), with its local-best addressing, scalar argmin and pinned
+// wave id.
+template <class Topo, int MODE, int TERMS, bool TUNED, class Rng>
+__device__ __forceinline__ void resident_iteration(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh, float* s_pb,
+                                                   int tid, int tid_upper, int wave, bool active, const PsoCoef& coef,
+                                                   int par, float (&x)[Topo::D], float (&v)[Topo::D], float& pbf,
+                                                   Rng& rng, uint32_t& gkey, int& bidx)
+{
+    constexpr int BLOCK = kResidentMaxThreads<Topo::D>();
+    constexpr int KV = kVelLds<Topo, MODE, TERMS>();
+    compiler_fence();
+    if constexpr ((TERMS & kTermColliders) && IKPSO_COLLIDE_RELOAD) {
+        // the chain constants re-read from the kernarg segment every iteration (kernarg_cc)
+        const ChainConsts<Topo::J>& cci = kernarg_cc<Topo::J>();
+        swarm_step<Topo, MODE, TERMS, BLOCK, KV>(cci, sh, s_pb, tid, x, v, pbf, pso_coef(cci), rng);
+    } else {
+        swarm_step<Topo, MODE, TERMS, BLOCK, KV, TUNED>(cc, sh, s_pb, tid, x, v, pbf, coef, rng, tid_upper);
+    }
+
+    // thrust::min_element + `globalMin > currentGlobalMin` (src/kernel.cu:315-323)
+    const uint32_t bmin = swarm_argmin<TUNED>(sh, par, active ? ordered_key(pbf) : 0xFFFFFFFFu, &bidx, wave);
+    if (bmin < gkey) {  // uniform across the workgroup
+        gkey = bmin;
+        if constexpr (TUNED)
+            copy_gbest<Topo, BLOCK>(sh, s_pb, bidx, wave);
+        else
+            copy_gbest<Topo, BLOCK>(sh, s_pb, bidx);
+        __syncthreads();
+    }
+}
+
 // The kernel body over its LDS: the per-swarm uniforms `sh` and the local-best
 // positions s_pb[d * BLOCK + lane] (read once per iteration by the update,
 // written on improvement; consecutive lanes hit consecutive banks).
@@ -419,24 +488,33 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
     // threshold (io.stop_key; 0 = never).  Tested after the first copy and after each
     // iteration's update; gkey is uniform, so the whole workgroup leaves together and what
     // follows is what a run of `it` iterations does.
+    constexpr bool UNROLL = kUnrollIterations<Topo, MODE, TERMS, STOP>;
+    const int wave = UNROLL ? wave_id_pinned() : 0;  // (the other builds read it where they use it)
+    const int tid_upper = UNROLL ? PbLane<BLOCK, UNROLL>::upper_lane(tid) : 0;
+    // (the iteration is a function, not a lambda over these locals: with x, v and the generator captured
+    // by reference the compiler contracted other products of the residual below into its FMAs, 1-2 ulp away)
     int it = 0;
-    for (; it < io.iterations && (!STOP || gkey > io.stop_key); ++it) {
-        compiler_fence();
-        if constexpr ((TERMS & kTermColliders) && IKPSO_COLLIDE_RELOAD) {
-            // the chain constants re-read from the kernarg segment every iteration (kernarg_cc)
-            const ChainConsts<Topo::J>& cci = kernarg_cc<Topo::J>();
-            swarm_step<Topo, MODE, TERMS, BLOCK, KV>(cci, sh, s_pb, tid, x, v, pbf, pso_coef(cci), rng);
-        } else {
-            swarm_step<Topo, MODE, TERMS, BLOCK, KV>(cc, sh, s_pb, tid, x, v, pbf, coef, rng);
+    if constexpr (UNROLL) {
+        // Two iterations per trip, then one for an odd count.  The compiler's update leaves every
+        // velocity in its addend's register (a v_fmac), and the 63 draws of an iteration turn the
+        // generator's five words by three places: in the rolled loop the back edge copies them all
+        // home, one v_mov each.  The second copy starts where the first one ended, so only what
+        // has not come round after two iterations is copied.  Same operations in the same order.
+        for (; it + 2 <= io.iterations; it += 2) {
+            resident_iteration<Topo, MODE, TERMS, UNROLL>(cc, sh, s_pb, tid, tid_upper, wave, active, coef, 1, x, v,
+                                                          pbf, rng, gkey, bidx);
+            resident_iteration<Topo, MODE, TERMS, UNROLL>(cc, sh, s_pb, tid, tid_upper, wave, active, coef, 0, x, v,
+                                                          pbf, rng, gkey, bidx);
         }
-
-        // thrust::min_element + `globalMin > currentGlobalMin` (src/kernel.cu:315-323)
-        const uint32_t bmin = swarm_argmin(sh, (it + 1) & 1, active ? ordered_key(pbf) : 0xFFFFFFFFu, &bidx);
-        if (bmin < gkey) {  // uniform across the workgroup
-            gkey = bmin;
-            copy_gbest<Topo, BLOCK>(sh, s_pb, bidx);
-            __syncthreads();
+        if (it < io.iterations) {
+            resident_iteration<Topo, MODE, TERMS, UNROLL>(cc, sh, s_pb, tid, tid_upper, wave, active, coef, 1, x, v,
+                                                          pbf, rng, gkey, bidx);
+            ++it;
         }
+    } else {
+        for (; it < io.iterations && (!STOP || gkey > io.stop_key); ++it)
+            resident_iteration<Topo, MODE, TERMS, UNROLL>(cc, sh, s_pb, tid, tid_upper, wave, active, coef,
+                                                          (it + 1) & 1, x, v, pbf, rng, gkey, bidx);
     }
 
     // outputs: Coordinates result (updateGlobalBestCoordsKernel) + fitness + residual

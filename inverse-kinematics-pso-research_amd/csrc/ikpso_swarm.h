@@ -190,6 +190,14 @@ struct Planes {
 // kept live across the loop (the compiler spilled it, and the reload sat on
 // the barrier's critical path).
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+// The wave id taken once and held in a scalar register the compiler cannot derive again from
+// threadIdx (which it would otherwise keep live, or spill, across an iteration loop).
+__device__ __forceinline__ int wave_id_pinned()
+{
+    int w = wave_id();
+    asm("" : "+s"(w));
+    return w;
+}
 
 // Lane id recomputed at the point of use (two VALU ops): an opaque asm, so the
 // compiler can neither hoist it out of the iteration loop nor keep it live
@@ -201,12 +209,15 @@ __device__ __forceinline__ int lane_id_here()
     return lane;
 }
 
-template <class SH>
-__device__ __forceinline__ uint32_t swarm_argmin(SH& sh, int par, uint32_t key, int* out_idx)
+// SCALAR (the unrolled resident build): the four row minima are combined on the scalar unit
+// (wave_min_u32_scalar), so the swarm minimum and the caller's running best are scalars, and
+// the wave id is the caller's (wave_id_pinned), not read from threadIdx in every iteration.
+template <bool SCALAR = false, class SH>
+__device__ __forceinline__ uint32_t swarm_argmin(SH& sh, int par, uint32_t key, int* out_idx, int wave_pinned = 0)
 {
-    const int lane = lane_id_here(), wave = wave_id();
+    const int lane = lane_id_here(), wave = SCALAR ? wave_pinned : wave_id();
     const int nwaves = blockDim.x >> 6;
-    const uint32_t wmin = wave_min_u32(key);
+    const uint32_t wmin = SCALAR ? wave_min_u32_scalar(key) : wave_min_u32(key);
     const int first = wave_first_lane_eq(key, wmin);
     if (lane == 0) {
         sh.key[par][wave] = wmin;
@@ -214,22 +225,28 @@ __device__ __forceinline__ uint32_t swarm_argmin(SH& sh, int par, uint32_t key, 
     }
     __syncthreads();
     const uint32_t k2 = lane < nwaves ? sh.key[par][lane] : 0xFFFFFFFFu;
-    const uint32_t bmin = wave_min_u32(k2);
+    const uint32_t bmin = SCALAR ? wave_min_u32_scalar(k2) : wave_min_u32(k2);
     *out_idx = __builtin_amdgcn_readfirstlane(sh.idx[par][wave_first_lane_eq(k2, bmin)]);
     return bmin;
 }
 
 // sh.g = local best of particle `idx` (updateGlobalBestCoordsKernel,
 // src/kernel.cu:268-277), copied by the first wave; the caller barriers.
+// (wave: the calling wave's id)
 template <class Topo, int BLOCK>
-__device__ __forceinline__ void copy_gbest(SwarmShared<Topo>& sh, const float* s_pb, int idx)
+__device__ __forceinline__ void copy_gbest(SwarmShared<Topo>& sh, const float* s_pb, int idx, int wave)
 {
     constexpr int D = Topo::D;
     static_assert(D <= 64, "one wave copies the global best");
-    if (wave_id() == 0) {
+    if (wave == 0) {
         const int lane = lane_id_here();
         if (lane < D) sh.g[lane] = s_pb[lane * BLOCK + idx];
     }
+}
+template <class Topo, int BLOCK>
+__device__ __forceinline__ void copy_gbest(SwarmShared<Topo>& sh, const float* s_pb, int idx)
+{
+    copy_gbest<Topo, BLOCK>(sh, s_pb, idx, wave_id());
 }
 
 // Term set of a chain for the kernel specialisation (see FitnessAcc): a masked

@@ -95,8 +95,8 @@ def main():
     for p in a.libs:
         t = np.array(times[p])
         ups = B * P * I / (np.median(t) / 1e3)
-        print(f"{Path(p).name:40s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  "
-              f"{ups:.3e} upd/s  mean_fit {results[p]:.6f}")
+        print(f"{Path(p).name:40s} median {np.median(t):8.3f} ms  min {t.min():8.3f}  max {t.max():8.3f}  "
+              f"spread {t.max() - t.min():6.3f}  {ups:.3e} upd/s  mean_fit {results[p]:.6f}")
 
 
 if __name__ == "__main__":
