@@ -258,6 +258,36 @@ ikpso_status ikpso_solve_batch_until(ikpso_solver* solver, const float* targets,
                                      float* out_angles, float* out_fitness, float* out_residual,
                                      int32_t* out_iterations, void* stream);
 
+/* Follow a sequence of targets: `frames` solves of every swarm in one call, each
+ * warm-started from the answer of the one before (added after ABI 5; detect by
+ * symbol).  Layouts are time-major, so frame t of every buffer is what one
+ * solve_batch_until call takes:
+ *   targets        device, [T][B][E][3].
+ *   start_pose     device, [B][D] or NULL: frame 0's only (NULL: chain rotations).
+ *   out_angles     device, [T][B][D].
+ *   out_fitness    device, [T][B].
+ *   out_residual   device, [T][B] or NULL.
+ *   out_iterations device, [T][B] or NULL.
+ * Contract: frame t of swarm b is ikpso_solve_batch_until on targets[t] with
+ * max_iterations and stop_fitness, its start_pose the caller's for t == 0 and
+ * out_angles[t-1] for t > 0 -- bit for bit, in FAST as in REFERENCE arithmetic,
+ * for the outputs, the iteration counts and the generator states left in the
+ * solver after the last frame.  Every frame is a fresh swarm (positions and rest
+ * pose at its start, velocities drawn, local bests at the positions); only the
+ * generators carry on from frame to frame.  A negative stop_fitness never stops;
+ * NaN is IKPSO_ERR_INVALID_ARG, even with nothing to solve.  frames == 0 or
+ * num_swarms == 0 returns IKPSO_OK with no device work; frames > 0 needs targets
+ * and out_angles.  Stream-ordered; does not synchronise.
+ * The resident family runs the whole call in one launch: a swarm stays on its CU
+ * and its generator states in registers for all frames.  A streaming solver, or
+ * one that AUTO routed to the cooperative family, runs one streaming solve per
+ * frame; a solver created with IKPSO_KERNEL_COOP gets IKPSO_ERR_UNSUPPORTED.  A
+ * pending cooperative solve is settled first. */
+ikpso_status ikpso_solve_track(ikpso_solver* solver, const float* targets, const float* start_pose,
+                               int64_t num_swarms, int32_t frames, int32_t max_iterations, float stop_fitness,
+                               float* out_angles, float* out_fitness, float* out_residual,
+                               int32_t* out_iterations, void* stream);
+
 /* Settle the last solve_batch (ABI >= 3).  After a cooperative-family solve:
  * wait for it and, if a group gave up (the GPU shared with other work), restore
  * the generator states from the snapshot taken before the launch and re-run the
@@ -300,8 +330,8 @@ int ikpso_solver_effectors(const ikpso_solver* solver);
 int ikpso_solver_collider_count(const ikpso_solver* solver);
 /* Name of the kernel variant the solver dispatches to (family / topology); after a
  * solve_batch that AUTO routed to the cooperative latency variant (a few swarms),
- * that variant's name until the next solve; after a solve_batch_until that ran the
- * streaming kernels for a cooperative solver, theirs. */
+ * that variant's name until the next solve; after a solve_batch_until or a
+ * solve_track that ran the streaming kernels for a cooperative solver, theirs. */
 const char* ikpso_solver_kernel_name(const ikpso_solver* solver);
 
 int ikpso_abi_version(void);

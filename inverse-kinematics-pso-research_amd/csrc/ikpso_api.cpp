@@ -899,9 +899,11 @@ ikpso_status solve_streaming(ikpso_solver* s, void** ws, size_t* ws_bytes, const
 // The batch on the resident kernel: one launch, one workgroup per swarm.
 ikpso_status solve_resident(ikpso_solver* s, const float* targets, const float* start_pose, int64_t num_swarms,
                             int32_t iterations, float* out_angles, float* out_fitness, float* out_residual,
-                            hipStream_t hs, uint32_t stop_key = 0, int32_t* out_iterations = nullptr)
+                            hipStream_t hs, uint32_t stop_key = 0, int32_t* out_iterations = nullptr,
+                            int32_t frames = 0)
 {
     SwarmIO io{};
+    io.frames = frames;  // > 0: ikpso_solve_track, every buffer but start_pose time-major
     io.targets = targets;
     io.start_pose = start_pose;
     io.rng = s->rng;
@@ -1372,6 +1374,45 @@ ikpso_status ikpso_solve_batch_until(ikpso_solver* s, const float* targets, cons
                               out_residual, hs, stop_key, out_iterations);
     return solve_streaming(s, &s->ws, &s->ws_bytes, targets, start_pose, num_swarms, max_iterations, out_angles,
                            out_fitness, out_residual, hs, stop_key, out_iterations);
+}
+
+// The frame loop of ikpso_solve_batch_until calls in one call.  Resident family: one launch,
+// the loop inside the kernel (swarm_track_body).  Streaming (also for a solver AUTO routed to
+// the cooperative family, as in solve_batch_until): the loop here, one streaming solve per
+// frame over pointer offsets, so the contract holds by construction.
+ikpso_status ikpso_solve_track(ikpso_solver* s, const float* targets, const float* start_pose, int64_t num_swarms,
+                               int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
+                               float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
+{
+    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
+        return IKPSO_ERR_INVALID_ARG;
+    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
+    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
+    if (num_swarms > s->capacity || !s->rng) return IKPSO_ERR_INVALID_ARG;  // seed first
+    if (num_swarms > 0x7fffffff) return IKPSO_ERR_INVALID_ARG;
+    if (s->requested == IKPSO_KERNEL_COOP) return IKPSO_ERR_UNSUPPORTED;
+    IKPSO_HIP(take_pending_error());
+    const hipStream_t hs = (hipStream_t)stream;
+    if (s->pending.active) {  // the previous cooperative solve was not synced: settle it first
+        const ikpso_status st = ikpso_solver_sync(s);
+        if (st != IKPSO_OK) return st;
+    }
+    const uint32_t stop_key = stop_fitness < 0.0f ? 0u : ordered_key_host(stop_fitness);  // negative: never stop
+    s->last_latency = false;
+    s->last_stream = s->family != IKPSO_KERNEL_RESIDENT;
+    if (!s->last_stream)
+        return solve_resident(s, targets, start_pose, num_swarms, max_iterations, out_angles, out_fitness,
+                              out_residual, hs, stop_key, out_iterations, frames);
+    const int64_t B = num_swarms, nt = B * s->chain.E * 3, na = B * s->chain.dof();  // one frame of targets, of angles
+    for (int64_t t = 0; t < frames; ++t) {
+        const ikpso_status st = solve_streaming(
+            s, &s->ws, &s->ws_bytes, targets + t * nt, t ? out_angles + (t - 1) * na : start_pose, B, max_iterations,
+            out_angles + t * na, out_fitness ? out_fitness + t * B : nullptr,
+            out_residual ? out_residual + t * B : nullptr, hs, stop_key,
+            out_iterations ? out_iterations + t * B : nullptr);
+        if (st != IKPSO_OK) return st;
+    }
+    return IKPSO_OK;
 }
 
 // ordered_key_host / key_to_float, for the tests (not part of the declared ABI)

@@ -1,0 +1,10 @@
+// ikpso_inst_track_serial_b_ref.hip -- the resident track kernels (ikpso_solve_track) of serial chains of 9, 10, 11 joints with a tip effector.
+#include "ikpso_topo_impl.h"
+
+namespace ikpso {
+#if IKPSO_WITH_DH
+template struct TrackOps<TopoSerialTip<9>, IKPSO_ARITH_REFERENCE>;
+template struct TrackOps<TopoSerialTip<10>, IKPSO_ARITH_REFERENCE>;
+template struct TrackOps<TopoSerialTip<11>, IKPSO_ARITH_REFERENCE>;
+#endif
+}  // namespace ikpso

@@ -1,0 +1,10 @@
+// ikpso_inst_track_serial_c_ref.hip -- the resident track kernels (ikpso_solve_track) of serial chains of 12, 13, 14 joints with a tip effector.
+#include "ikpso_topo_impl.h"
+
+namespace ikpso {
+#if IKPSO_WITH_DH
+template struct TrackOps<TopoSerialTip<12>, IKPSO_ARITH_REFERENCE>;
+template struct TrackOps<TopoSerialTip<13>, IKPSO_ARITH_REFERENCE>;
+template struct TrackOps<TopoSerialTip<14>, IKPSO_ARITH_REFERENCE>;
+#endif
+}  // namespace ikpso

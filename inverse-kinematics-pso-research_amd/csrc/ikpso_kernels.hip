@@ -97,7 +97,8 @@ hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hip
     hipError_t err = hipErrorInvalidValue;
     const bool ok = visit_topology(ch, [&](auto topo) {
         using T = decltype(topo);
-        err = TopoOps<T>::resident(ch, mode, io, block, stream);
+        err = io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
+                            : TopoOps<T>::resident(ch, mode, io, block, stream);
     });
     return ok ? err : hipErrorInvalidValue;
 }

@@ -103,6 +103,11 @@ struct SwarmIO {
     // fitness has key 0.
     uint32_t stop_key;
     int32_t* out_iterations;  // [B] iterations each swarm ran, or null
+    // Resident track kernel only (ikpso_solve_track): frames solved in the one launch, each
+    // warm-started from the previous one's answer.  targets and the out_* buffers are then
+    // time-major ([frames][B]...), start_pose is frame 0's.  0: the plain and stopping kernels,
+    // which never read it.
+    int32_t frames;
 };
 
 // Streaming (state-in-HBM) kernels: one launch per PSO iteration over every

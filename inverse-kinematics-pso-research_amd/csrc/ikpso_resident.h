@@ -547,6 +547,90 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
 }
 
 
+// The track kernel's body (ikpso_solve_track): io.frames frames of one swarm in one workgroup.
+// Frame t is the stopping kernel's solve of targets[t] warm-started from frame t-1's answer
+// (frame 0: from start_pose), bit for bit what a loop of ikpso_solve_batch_until calls over the
+// time-major buffers computes -- without the launches, and with the generator states loaded
+// once before the first frame and stored once after the last.  Every frame is a fresh swarm
+// (init_particle); only the generators carry on.
+// The hand-off goes through LDS: sh.rest[d] of a free dimension becomes answer_angle(sh.g[d])
+// -- the float store_angles writes, radians -- times the staging's unit factor, exactly what
+// stage_swarm_inputs would read back from out_angles.  In the revolution-unit builds that is not
+// sh.g[d]: the product with 2 pi, the inside-bounds clamp and the product with 1/2pi round.
+// Locked dimensions keep the chain's rest value, staged before the first frame.
+// Barriers: one after a frame's last reads of sh.g, sh.tgt, sh.key and sh.idx (the outputs and
+// the residual), before the next frame's rest and targets are written; one after those, before
+// init_particle reads them and the parity-0 argmin writes sh.key again.
+template <class Topo, int MODE, int TERMS>
+__device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc, const SwarmIO& io,
+                                                 SwarmShared<Topo>& sh, float* const s_pb)
+{
+    constexpr int D = Topo::D;
+    constexpr int BLOCK = kResidentMaxThreads<D>();
+    constexpr int KV = kVelLds<Topo, MODE, TERMS>();
+    constexpr float sc = (TERMS & kTermRev) ? kInv2Pi : 1.0f;
+    const int64_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int P = io.P;
+    const bool active = tid < P;
+
+    // the frame-invariant uniforms and frame 0's warm start (stage_swarm_inputs' expressions)
+    for (int d = tid; d < D; d += blockDim.x) {
+        sh.lo[d] = cc.lo[d] * sc;
+        sh.hi[d] = cc.hi[d] * sc;
+        sh.rest[d] =
+            (io.start_pose && dim_free(cc, d) ? io.start_pose[b * cc.dfree + dim_rank(cc, d)] : cc.rest[d]) * sc;
+    }
+    stage_chain_uniforms<Topo, TERMS>(cc, sh);
+
+    RngFor<TERMS> rng{0, 0, 0, 0, 0, 0};
+    if (active) load_rng(rng, io.rng + b * P + tid);
+
+    const PsoCoef coef = pso_coef(cc);
+    float* const s_v = s_pb + D * BLOCK;  // (kVelLds)
+    for (int32_t t = 0; t < io.frames; ++t) {
+        const int64_t cell = (int64_t)t * io.num_swarms + b;  // (frame, swarm) in the time-major buffers
+        stage_swarm_targets<Topo, TERMS>(cc, io.targets + cell * cc.num_eff * 3, sh);
+        __syncthreads();
+
+        // initParticlesKernel, initLocalBests, first argmin and global-best copy (swarm_resident_body)
+        float x[D], v[D];
+        init_particle<Topo, TERMS, BLOCK>(cc, sh, s_pb, tid, x, v, rng);
+#pragma unroll
+        for (int d = 0; d < KV; ++d) s_v[d * BLOCK + tid] = v[d];
+        float pbf = fitness<Topo, MODE, TERMS>(cc, x, sh.rest, sh.tgt, nullptr, sh.dh, sh.soft);
+        int bidx;
+        uint32_t gkey = swarm_argmin(sh, 0, active ? ordered_key(pbf) : 0xFFFFFFFFu, &bidx);
+        copy_gbest<Topo, BLOCK>(sh, s_pb, bidx);
+        __syncthreads();
+
+        // the stopping kernel's iteration loop
+        int it = 0;
+        for (; it < io.iterations && gkey > io.stop_key; ++it)
+            resident_iteration<Topo, MODE, TERMS, false>(cc, sh, s_pb, tid, 0, 0, active, coef, (it + 1) & 1, x, v, pbf,
+                                                         rng, gkey, bidx);
+
+        // the frame's outputs
+        compiler_fence();
+        const float answer = tid < D ? answer_angle<Topo, TERMS>(cc, tid, sh.g[tid]) : 0.0f;
+        const bool is_free = tid < D && dim_free(cc, tid);
+        if (is_free) io.out_angles[cell * cc.dfree + dim_rank(cc, tid)] = answer;
+        if (tid == 0 && io.out_fitness) io.out_fitness[cell] = key_to_float(gkey);
+        if (tid == 0 && io.out_iterations) io.out_iterations[cell] = it;
+        if (io.out_residual && tid < 64) {
+            float g[D];
+#pragma unroll
+            for (int d = 0; d < D; ++d) g[d] = sh.g[d];
+            const float r = residual<Topo, MODE, TERMS>(cc, g, sh.tgt, sh.dh);
+            if (tid == 0) io.out_residual[cell] = r;
+        }
+        __syncthreads();
+        if (is_free) sh.rest[tid] = answer * sc;  // the next frame's warm start
+    }
+    if (active) store_rng(rng, io.rng + b * P + tid);
+}
+
+
 #ifndef IKPSO_COLLIDE_UNIFORM
 #define IKPSO_COLLIDE_UNIFORM 1  // the reference scene with colliders: a uniform-bounds FAST build (79.2 -> 77.2 ms)
 #endif
@@ -564,10 +648,13 @@ __device__ __forceinline__ void swarm_resident_body(const ChainConsts<Topo::J>& 
 template <class Topo>
 constexpr int kResidentMinWaves = Topo::kDH ? 8 : 1;
 
-template <class Topo, int MODE, int TERMS, bool STOP = false>
+// TRACK (ikpso_solve_track): the stopping kernel's twin with the frame loop (swarm_track_body),
+// instantiated in units of its own (TrackOps, ikpso_inst_track_*.hip).
+template <class Topo, int MODE, int TERMS, bool STOP = false, bool TRACK = false>
 __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWaves<Topo>)
     k_swarm_resident(const ChainConsts<Topo::J> cc, const SwarmIO io)
 {
+    static_assert(STOP || !TRACK, "the track kernel stops per frame");
     // local bests [d][lane], then the collider builds' LDS velocities (kVelLds)
     constexpr int NPB = (Topo::D + kVelLds<Topo, MODE, TERMS>()) * kResidentMaxThreads<Topo::D>();
     if constexpr (Topo::kGeneric) {
@@ -575,10 +662,16 @@ __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWa
         // LDS object (an illegal flat-to-LDS check)
         __shared__ SwarmShared<Topo> sh;
         __shared__ float s_pb[NPB];
-        swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, sh, s_pb);
+        if constexpr (TRACK)
+            swarm_track_body<Topo, MODE, TERMS>(cc, io, sh, s_pb);
+        else
+            swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, sh, s_pb);
     } else {
         __shared__ SwarmLds<Topo, NPB> lds;  // uniforms below 64 KiB (SwarmLds)
-        swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, lds.sh, lds.pb);
+        if constexpr (TRACK)
+            swarm_track_body<Topo, MODE, TERMS>(cc, io, lds.sh, lds.pb);
+        else
+            swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, lds.sh, lds.pb);
     }
 }
 
@@ -623,19 +716,21 @@ __global__ void __launch_bounds__(256) k_evaluate(const ChainConsts<Topo::J> cc,
 
 // --------------------------------------------------------------- dispatch
 // One resident build: its plain kernel, or for ikpso_solve_batch_until (a threshold or an
-// iteration-count output) its stopping twin.
-template <class Topo, int MODE, int TERMS>
+// iteration-count output) its stopping twin.  TRACK: its track twin alone (ikpso_solve_track).
+template <class Topo, int MODE, int TERMS, bool TRACK = false>
 inline hipError_t launch_resident_build(const ChainConsts<Topo::J>& cc, const SwarmIO& io, dim3 grid, dim3 threads,
                                         hipStream_t stream)
 {
-    if (io.stop_key != 0 || io.out_iterations)
+    if constexpr (TRACK)
+        hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, TERMS, true, true>), grid, threads, 0, stream, cc, io);
+    else if (io.stop_key != 0 || io.out_iterations)
         hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, TERMS, true>), grid, threads, 0, stream, cc, io);
     else
         hipLaunchKernelGGL((k_swarm_resident<Topo, MODE, TERMS, false>), grid, threads, 0, stream, cc, io);
     return hipGetLastError();
 }
 
-template <class Topo, int MODE>
+template <class Topo, int MODE, bool TRACK = false>
 inline hipError_t run_resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
 {
     const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
@@ -651,43 +746,43 @@ inline hipError_t run_resident(const ChainHost& ch, const SwarmIO& io, int block
     const int terms = term_set(ch);
     hipError_t err = hipSuccess;
     if (dh_terms<Topo>(terms, &err, [&](auto t) {
-            return launch_resident_build<Topo, MODE, decltype(t)::value | kTermRev>(cc, io, grid, threads, stream);
+            return launch_resident_build<Topo, MODE, decltype(t)::value | kTermRev, TRACK>(cc, io, grid, threads, stream);
         }))
         return err;
     if constexpr (!Topo::kGeneric && !Topo::kDH && MODE == IKPSO_ARITH_FAST) {
         if constexpr (std::is_same_v<Topo, TopoRef7>) {  // the reference scene's [0, 2pi] limits
             if (terms == kTermUniformBounds && ch.unit_rev_bounds)
-                return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev | kFastUnitBounds>(
+                return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev | kFastUnitBounds, TRACK>(
                     cc, io, grid, threads, stream);
         }
         if (terms == kTermUniformBounds)
-            return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev>(cc, io, grid, threads, stream);
+            return launch_resident_build<Topo, MODE, kTermUniformBounds | kFastRev, TRACK>(cc, io, grid, threads, stream);
         if constexpr (std::is_same_v<Topo, TopoRef7> && IKPSO_COLLIDE_UNIFORM) {
             // the reference scene with colliders (the bench's collide leg): no runtime term tests, the clamp
             // bounds uniform (the separating-axis builds: colliders that are rotations, angles in the unit's range)
             if (terms == (kTermUniformBounds | kTermColliders) && ch.num_coll > 0 && ch.coll_obb && !ch.poly_trig)
-                return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermColliders>(cc, io, grid, threads,
+                return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermColliders, TRACK>(cc, io, grid, threads,
                                                                                               stream);
         }
         if constexpr (std::is_same_v<Topo, TopoSerialTip<20>>) {  // BASELINE config 5's symmetric soft limits
             if (terms == (kTermUniformBounds | kTermPenalty) && ch.sym_penalty)
                 return launch_resident_build<Topo, MODE,
-                                             kTermUniformBounds | kTermPenalty | kFastRev | kFastSymPenalty>(
+                                             kTermUniformBounds | kTermPenalty | kFastRev | kFastSymPenalty, TRACK>(
                     cc, io, grid, threads, stream);
         }
         if (terms == (kTermUniformBounds | kTermPenalty))
-            return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermPenalty | kFastRev>(cc, io, grid,
+            return launch_resident_build<Topo, MODE, kTermUniformBounds | kTermPenalty | kFastRev, TRACK>(cc, io, grid,
                                                                                                    threads, stream);
     }
     // REFERENCE on the reference scene (the bit-exact path the bench's reference_arith leg and the
     // recorded-trajectory replay run): no runtime term tests, the median clamp for ordered bounds
     if constexpr (std::is_same_v<Topo, TopoRef7> && MODE == IKPSO_ARITH_REFERENCE && IKPSO_REF_UNIFORM_BUILD) {
         if (terms == kTermUniformBounds && ch.ordered_bounds)
-            return launch_resident_build<Topo, MODE, kTermUniformBounds>(cc, io, grid, threads, stream);
+            return launch_resident_build<Topo, MODE, kTermUniformBounds, TRACK>(cc, io, grid, threads, stream);
     }
     (void)terms;
     return with_runtime_terms<Topo>(ch, [&](auto t) {
-        return launch_resident_build<Topo, MODE, decltype(t)::value>(cc, io, grid, threads, stream);
+        return launch_resident_build<Topo, MODE, decltype(t)::value, TRACK>(cc, io, grid, threads, stream);
     });
 }
 

@@ -72,20 +72,13 @@ struct SwarmLds {
     float pb[NPB];  // local bests [d][lane] (the cooperative long-chain build: velocities)
 };
 
-// start_pose: [B][dfree] over the free dimensions (the chain's mask).
-// kTermRev builds: the angles (rest pose, clamp and soft limits) in revolutions.
+// The effector targets of one swarm (t: its [E][3] block, or null for the chain's own), per
+// node, moved into the origin's frame where the build evaluates there.
 template <class Topo, int TERMS = 0>
-__device__ __forceinline__ void stage_swarm_inputs(const ChainConsts<Topo::J>& cc, const float* targets,
-                                                   const float* start_pose, int64_t b, SwarmShared<Topo>& sh)
+__device__ __forceinline__ void stage_swarm_targets(const ChainConsts<Topo::J>& cc, const float* t,
+                                                    SwarmShared<Topo>& sh)
 {
-    constexpr int D = Topo::D, J = Topo::J;
-    constexpr float sc = (TERMS & kTermRev) ? kInv2Pi : 1.0f;
-    const float* t = targets ? targets + b * (int64_t)cc.num_eff * 3 : nullptr;
-    for (int d = threadIdx.x; d < D; d += blockDim.x) {
-        sh.lo[d] = cc.lo[d] * sc;
-        sh.hi[d] = cc.hi[d] * sc;
-        sh.rest[d] = (start_pose && dim_free(cc, d) ? start_pose[b * cc.dfree + dim_rank(cc, d)] : cc.rest[d]) * sc;
-    }
+    constexpr int J = Topo::J;
     if constexpr (kOriginFrame<Topo, TERMS>) {
         // targets moved into the origin's frame: t' = M0^T (t - p0) (root_frame_sc)
         const float* m = cc.m0;
@@ -104,6 +97,15 @@ __device__ __forceinline__ void stage_swarm_inputs(const ChainConsts<Topo::J>& c
             sh.tgt[n] = t ? (s >= 0 ? t[3 * s + n % 3] : 0.0f) : cc.tgt0[n];
         }
     }
+}
+
+// The uniforms that depend on the chain alone: folded-chain constants, soft limits and the
+// near-collider table.
+template <class Topo, int TERMS = 0>
+__device__ __forceinline__ void stage_chain_uniforms(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh)
+{
+    constexpr int J = Topo::J;
+    constexpr float sc = (TERMS & kTermRev) ? kInv2Pi : 1.0f;
     if constexpr (Topo::kDH)
         for (int n = threadIdx.x; n < 12 * J + 4; n += blockDim.x) sh.dh[n] = cc.aux[cc.dh_off + n];
     if (cc.use_penalty)
@@ -118,6 +120,24 @@ __device__ __forceinline__ void stage_swarm_inputs(const ChainConsts<Topo::J>& c
                 sh.near4[4 * n + 3] = cc.coll_lim[k * cc.num_coll + i];
             }
         }
+}
+
+// start_pose: [B][dfree] over the free dimensions (the chain's mask).
+// kTermRev builds: the angles (rest pose, clamp and soft limits) in revolutions.
+template <class Topo, int TERMS = 0>
+__device__ __forceinline__ void stage_swarm_inputs(const ChainConsts<Topo::J>& cc, const float* targets,
+                                                   const float* start_pose, int64_t b, SwarmShared<Topo>& sh)
+{
+    constexpr int D = Topo::D;
+    constexpr float sc = (TERMS & kTermRev) ? kInv2Pi : 1.0f;
+    const float* t = targets ? targets + b * (int64_t)cc.num_eff * 3 : nullptr;
+    for (int d = threadIdx.x; d < D; d += blockDim.x) {
+        sh.lo[d] = cc.lo[d] * sc;
+        sh.hi[d] = cc.hi[d] * sc;
+        sh.rest[d] = (start_pose && dim_free(cc, d) ? start_pose[b * cc.dfree + dim_rank(cc, d)] : cc.rest[d]) * sc;
+    }
+    stage_swarm_targets<Topo, TERMS>(cc, t, sh);
+    stage_chain_uniforms<Topo, TERMS>(cc, sh);
 }
 
 // An angle of the kernel's units in radians (kTermRev: revolutions * 2 pi).
@@ -138,17 +158,23 @@ __device__ __forceinline__ float radians(float a)
 // land an ulp out).  An answer outside them -- the start pose itself, which the
 // reference never clamps (src/kernel.cu:223-266), winning every iteration -- is
 // returned as it is, as the reference returns it.
+// answer_angle: the value written for dimension d -- one expression for the store and for
+// the track kernel's hand-off, whose next frame starts from exactly the float stored.
+template <class Topo, int TERMS>
+__device__ __forceinline__ float answer_angle(const ChainConsts<Topo::J>& cc, int d, float g)
+{
+    if constexpr (TERMS & kTermRev) {
+        const bool inside = g >= cc.lo[d] * kInv2Pi && g <= cc.hi[d] * kInv2Pi;
+        g *= k2Pi;
+        if (inside) g = fminf(fmaxf(g, cc.lo[d]), cc.hi[d]);
+    }
+    return g;
+}
+
 template <class Topo, int TERMS = 0>
 __device__ __forceinline__ void store_angles(const ChainConsts<Topo::J>& cc, float* out, int64_t b, int d, float g)
 {
-    if (d < Topo::D && dim_free(cc, d)) {
-        if constexpr (TERMS & kTermRev) {
-            const bool inside = g >= cc.lo[d] * kInv2Pi && g <= cc.hi[d] * kInv2Pi;
-            g *= k2Pi;
-            if (inside) g = fminf(fmaxf(g, cc.lo[d]), cc.hi[d]);
-        }
-        out[b * cc.dfree + dim_rank(cc, d)] = g;
-    }
+    if (d < Topo::D && dim_free(cc, d)) out[b * cc.dfree + dim_rank(cc, d)] = answer_angle<Topo, TERMS>(cc, d, g);
 }
 
 __device__ __forceinline__ void compiler_fence() { asm volatile("" ::: "memory"); }

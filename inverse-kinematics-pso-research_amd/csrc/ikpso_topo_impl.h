@@ -1,4 +1,4 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>; include from the
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE> and TrackOps<Topo, MODE>; include from the
 // ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
@@ -13,6 +13,12 @@ template <class Topo, int MODE>
 hipError_t ModeOps<Topo, MODE>::resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
 {
     return run_resident<Topo, MODE>(ch, io, block, s);
+}
+
+template <class Topo, int MODE>
+hipError_t TrackOps<Topo, MODE>::resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
+{
+    return run_resident<Topo, MODE, true>(ch, io, block, s);
 }
 
 template <class Topo, int MODE>

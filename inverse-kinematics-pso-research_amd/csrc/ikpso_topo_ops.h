@@ -18,6 +18,13 @@ struct ModeOps {
     static hipError_t coop(const ChainHost& ch, const SwarmIO& io, hipStream_t stream);
 };
 
+// The resident family's track kernels (ikpso_solve_track), apart from ModeOps so that their
+// instantiations sit in translation units of their own (ikpso_inst_track_*.hip).
+template <class Topo, int MODE>
+struct TrackOps {
+    static hipError_t resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -32,6 +39,14 @@ struct TopoOps {
             return hipErrorNotSupported;
         }
         return Fast::resident(ch, io, block, s);
+    }
+    static hipError_t track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    {
+        if (mode == IKPSO_ARITH_REFERENCE) {
+            if constexpr (kRef) return TrackOps<Topo, IKPSO_ARITH_REFERENCE>::resident(ch, io, block, s);
+            return hipErrorNotSupported;
+        }
+        return TrackOps<Topo, IKPSO_ARITH_FAST>::resident(ch, io, block, s);
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {

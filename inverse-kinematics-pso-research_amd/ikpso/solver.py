@@ -315,6 +315,40 @@ class BatchSolver:
                    "ikpso_solve_batch_until")
         return angles, fitness, res, iters
 
+    def solve_track(self, targets, start_pose=None, iterations: Optional[int] = None,
+                    stop_fitness: Optional[float] = None, residual: bool = True, stream=None):
+        """B swarms following T waypoints each (ikpso_solve_track): targets is device [T, B, E, 3],
+        time-major; frame t of swarm b is solve_until on targets[t] with `iterations` as its
+        maximum (None: the solver's PSOConfig.iterations), warm-started from start_pose (device
+        [B, D] or None: the chain rotations) for t = 0 and from frame t-1's answer after that, bit
+        for bit -- outputs, iteration counts and the generator states left in the solver.  Every
+        frame is a fresh swarm; only the generators carry on.  stop_fitness=None never stops.
+        Returns (angles [T, B, D], fitness [T, B], residual [T, B] or None, iterations [T, B]
+        int32) device tensors.  The resident family runs the whole track in one launch, the
+        streaming kernels one solve per frame; a kernel="coop" solver raises (unsupported
+        configuration).  Stream-ordered, asynchronous."""
+        torch = _torch()
+        if targets is None or targets.dim() != 4:
+            raise ValueError(f"targets must be [T, B, {self.effectors}, 3]")
+        T, B = int(targets.shape[0]), int(targets.shape[1])
+        it = self.pso.iterations if iterations is None else int(iterations)
+        stop = -1.0 if stop_fitness is None else float(stop_fitness)
+        if tuple(targets.shape) != (T, B, self.effectors, 3):
+            raise ValueError(f"targets must be [{T}, {B}, {self.effectors}, 3]")
+        if start_pose is not None and tuple(start_pose.shape) != (B, self.dof):
+            raise ValueError(f"start_pose must be [{B}, {self.dof}]")
+        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        angles = torch.empty((T, B, self.dof), dtype=torch.float32, device=dev)
+        fitness = torch.empty((T, B), dtype=torch.float32, device=dev)
+        res = torch.empty((T, B), dtype=torch.float32, device=dev) if residual else None
+        iters = torch.empty((T, B), dtype=torch.int32, device=dev)
+        for t, name in ((targets, "targets"), (start_pose, "start_pose")):
+            self._check_tensor(t, name, dev)
+        _abi.check(self._lib.ikpso_solve_track(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, T, it, stop,
+                                               _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res), _dev_ptr(iters),
+                                               _stream_handle(stream)), "ikpso_solve_track")
+        return angles, fitness, res, iters
+
     def sync(self) -> None:
         """ikpso_solver_sync: settle the last solve (see solve(sync=...))."""
         _abi.check(self._lib.ikpso_solver_sync(self._h), "ikpso_solver_sync")
