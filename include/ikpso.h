@@ -330,7 +330,9 @@ int ikpso_solver_effectors(const ikpso_solver* solver);
 int ikpso_solver_collider_count(const ikpso_solver* solver);
 /* Name of the kernel variant the solver dispatches to (family / topology); after a
  * solve_batch that AUTO routed to the cooperative latency variant (a few swarms),
- * that variant's name until the next solve; after a solve_batch_until or a
+ * that variant's name until the next solve (a long serial chain, whose chunks
+ * are the latency width already, runs and names the cooperative kernel itself
+ * there, whatever the number of swarms); after a solve_batch_until or a
  * solve_track that ran the streaming kernels for a cooperative solver, theirs. */
 const char* ikpso_solver_kernel_name(const ikpso_solver* solver);
 

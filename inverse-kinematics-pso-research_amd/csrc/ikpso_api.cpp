@@ -822,6 +822,10 @@ struct ikpso_solver {
     std::string kname;     // kernel family / topology, for ikpso_solver_kernel_name
     std::string kname_latency;  // the cooperative latency variant AUTO may pick per call
     bool last_latency = false;  // the last solve_batch ran the latency variant
+    // A resident AUTO solver of a long chain (256-lane chunks: no separate latency build) still
+    // takes the cooperative route for a swarm of one chunk: the name reported is that kernel's.
+    std::string kname_coop;
+    bool last_coop = false;     // the last solve_batch ran the cooperative kernel's throughput build
     std::string kname_stream;   // the streaming kernels solve_batch_until runs for an AUTO cooperative solver
     bool last_stream = false;   // the last solve ran them
     void* ws = nullptr;    // streaming / cooperative workspace
@@ -1195,6 +1199,7 @@ ikpso_status ikpso_solver_create(const ikpso_solver_desc* desc, ikpso_solver** o
     s->requested = desc->kernel;
     if (s->family >= 0) s->kname = kernel_name(sch, s->family);
     if (s->family >= 0) s->kname_stream = kernel_name(sch, IKPSO_KERNEL_STREAMING);
+    if (s->family >= 0) s->kname_coop = kernel_name(sch, IKPSO_KERNEL_COOP);
     if (s->family >= 0)
         s->kname_latency = kernel_name(sch, IKPSO_KERNEL_COOP) +
                            (coop_latency_split(sch) ? " (latency variant, generator waves)" : " (latency variant)");
@@ -1264,6 +1269,7 @@ ikpso_status ikpso_solve_batch(ikpso_solver* s, const float* targets, const floa
     const bool latency_coop = s->family == IKPSO_KERNEL_RESIDENT && s->requested == IKPSO_KERNEL_AUTO &&
                               prefer_latency_coop(ch, s->mode, s->P, num_swarms);
     s->last_latency = latency_coop;
+    s->last_coop = false;
     s->last_stream = false;
     if (s->family == IKPSO_KERNEL_RESIDENT && !latency_coop)
         return solve_resident(s, targets, start_pose, num_swarms, iterations, out_angles, out_fitness, out_residual,
@@ -1325,6 +1331,7 @@ ikpso_status ikpso_solve_batch(ikpso_solver* s, const float* targets, const floa
         // kCoopLatencyThreads wide too: only a block other than the throughput one is the latency plan)
         CoopGeometry geo;
         s->last_latency = coop_geometry(ch, s->mode, &geo) && T != geo.threads;
+        s->last_coop = !s->last_latency;
         IKPSO_HIP(launch_coop(ch, s->mode, io, hs));
         s->pending.active = true;
         s->pending.targets = targets;
@@ -1368,6 +1375,7 @@ ikpso_status ikpso_solve_batch_until(ikpso_solver* s, const float* targets, cons
     }
     const uint32_t stop_key = stop_fitness < 0.0f ? 0u : ordered_key_host(stop_fitness);  // negative: never stop
     s->last_latency = false;
+    s->last_coop = false;
     s->last_stream = s->family != IKPSO_KERNEL_RESIDENT;
     if (!s->last_stream)
         return solve_resident(s, targets, start_pose, num_swarms, max_iterations, out_angles, out_fitness,
@@ -1399,6 +1407,7 @@ ikpso_status ikpso_solve_track(ikpso_solver* s, const float* targets, const floa
     }
     const uint32_t stop_key = stop_fitness < 0.0f ? 0u : ordered_key_host(stop_fitness);  // negative: never stop
     s->last_latency = false;
+    s->last_coop = false;
     s->last_stream = s->family != IKPSO_KERNEL_RESIDENT;
     if (!s->last_stream)
         return solve_resident(s, targets, start_pose, num_swarms, max_iterations, out_angles, out_fitness,
@@ -1500,7 +1509,12 @@ int ikpso_solver_effectors(const ikpso_solver* s) { return s ? s->chain.E : 0; }
 int ikpso_solver_collider_count(const ikpso_solver* s) { return s ? s->chain.num_coll : 0; }
 const char* ikpso_solver_kernel_name(const ikpso_solver* s)
 {
-    return s ? (s->last_stream ? s->kname_stream : s->last_latency ? s->kname_latency : s->kname).c_str() : "";
+    return s ? (s->last_stream    ? s->kname_stream
+                : s->last_latency ? s->kname_latency
+                : s->last_coop    ? s->kname_coop
+                                  : s->kname)
+                   .c_str()
+             : "";
 }
 
 }  // extern "C"

@@ -87,8 +87,8 @@ def run_loop(make, targets, stop, start=None, iterations=IT):
     return out
 
 
-def median_threshold(make, targets, rows=slice(0, REACHABLE)):
-    return float(np.median(run_loop(make, targets, None)[1][:, rows]))
+def median_threshold(make, targets, rows=slice(0, REACHABLE), iterations=IT):
+    return float(np.median(run_loop(make, targets, None, iterations=iterations)[1][:, rows]))
 
 
 def assert_same(got, want):
