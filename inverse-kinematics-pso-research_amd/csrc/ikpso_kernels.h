@@ -47,7 +47,7 @@ namespace ikpso {
 // Ref7: the reference scene's tree with effectors on nodes 5..7; SerialTip:
 // serial chain with a single tip effector; Generic: anything else.
 // DH: a serial chain with a tip effector folded into its free angles (TopoDH;
-// built from a masked chain by the API layer, FAST arithmetic).
+// built from a masked chain by build_dh, ikpso_chain.cpp; FAST arithmetic).
 enum class TopoKind { Ref7, SerialTip, Generic, DH };
 
 // The chain as the kernels need it, parsed once from the caller's node table.
@@ -261,11 +261,11 @@ struct CoopGeometry {
     int threads = 0, blocks_per_cu = 0, cus = 0;
     bool latency_variant = false;  // a kCoopLatencyThreads build exists for this chain
 };
-bool coop_geometry(const ChainHost& ch, int mode, CoopGeometry* g);
-size_t coop_workspace_bytes(int ng, int G, int D, int block);
+bool coop_geometry(const ChainHost& ch, CoopGeometry* g);
+size_t coop_workspace_bytes(int ng, int G, int D);
 bool coop_latency_split(const ChainHost& ch);  // latency variant with generator waves
 int resident_max_threads(const ChainHost& ch);
-bool chain_supported(const ChainHost& ch);
+bool chain_supported(const ChainHost& ch);  // a compiled kernel exists (ikpso_chain.cpp)
 std::string kernel_name(const ChainHost& ch, int family);  // IKPSO_KERNEL_*
 
 }  // namespace ikpso

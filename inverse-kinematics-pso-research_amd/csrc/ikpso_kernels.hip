@@ -66,11 +66,6 @@ int resident_max_threads(const ChainHost& ch)
     return r;
 }
 
-bool chain_supported(const ChainHost& ch)
-{
-    return visit_topology(ch, [](auto) {});
-}
-
 std::string kernel_name(const ChainHost& ch, int family)
 {
     const char* fam = family == IKPSO_KERNEL_COOP ? "swarm_coop" : family == IKPSO_KERNEL_STREAMING
@@ -133,9 +128,8 @@ hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStre
 // Cooperative workgroups per CU: one for short chains (the kernel's LDS block is
 // at least 82 KiB, more than half of a CU's 160 KiB), two for long ones
 // (kCoopBlocksPerCU).
-bool coop_geometry(const ChainHost& ch, int mode, CoopGeometry* g)
+bool coop_geometry(const ChainHost& ch, CoopGeometry* g)
 {
-    (void)mode;
     bool spec = false;
     visit_topology(ch, [&](auto topo) {
         using T = decltype(topo);
@@ -179,7 +173,7 @@ bool coop_latency_split(const ChainHost& ch)
     return split;
 }
 
-size_t coop_workspace_bytes(int ng, int G, int D, int block)
+size_t coop_workspace_bytes(int ng, int G, int D)
 {
     return 8 * (size_t)ng * 2 * G * kCoopSlot(D) +
            256 + 3 * 256 + (IKPSO_COOP_TIMING ? 64 * (size_t)ng * G + 256 : 0);
