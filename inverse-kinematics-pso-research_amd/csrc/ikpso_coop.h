@@ -423,22 +423,20 @@ inline hipError_t coop_residency(ResidencyCache& cache, K kernel, int threads, i
     return hipSuccess;
 }
 
-// Launch: grid = NG * G workgroups, at most kCoopBlocksPerCU per CU.  Co-residency is
+// Launch: grid = NG * G workgroups of T lanes, at most want_per_cu per CU.  Co-residency is
 // checked here against the occupancy query (the check hipLaunchCooperativeKernel
 // would make; a plain launch gives the same residency without the cooperative
 // queue): an oversized grid is an error, never a hang.
-template <class Topo, int MODE, int TERMS, int T>
-inline hipError_t launch_coop_block(const ChainConsts<Topo::J>& cc, const SwarmIO& io, hipStream_t stream)
+// The plan assumed want_per_cu workgroups per CU; a build whose registers
+// admit fewer (the long chains' collider builds exceed 256 VGPRs) runs fewer
+// concurrent groups -- the slots carved for the plan's NG cover them.
+template <class K, class CC>
+inline hipError_t launch_coop_fitted(ResidencyCache& cache, K kernel, int T, int want_per_cu, const CC& cc,
+                                     const SwarmIO& io, hipStream_t stream)
 {
-    const auto kernel = &k_swarm_coop<Topo, MODE, TERMS, T>;
-    static ResidencyCache cache;
     int cus = 0, per_cu = 0;
     const hipError_t e = coop_residency(cache, kernel, T, &cus, &per_cu);
     if (e != hipSuccess) return e;
-    // The plan assumed kCoopBlocksPerCU workgroups per CU; a build whose registers
-    // admit fewer (the long chains' collider builds exceed 256 VGPRs) runs fewer
-    // concurrent groups -- the slots carved for the plan's NG cover them.
-    const int want_per_cu = kCoopMinWaves<Topo::D, T, TERMS> / (T >= 256 ? T / 256 : 1);
     const int fit = per_cu < want_per_cu ? per_cu : want_per_cu;
     if (fit < 1) return hipErrorCooperativeLaunchTooLarge;
     SwarmIO run = io;
@@ -448,6 +446,15 @@ inline hipError_t launch_coop_block(const ChainConsts<Topo::J>& cc, const SwarmI
     const int64_t grid = (int64_t)run.coop_ng * run.coop_g;
     hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(T), 0, stream, cc, run);
     return hipGetLastError();
+}
+
+// At most kCoopBlocksPerCU workgroups per CU (kCoopMinWaves).
+template <class Topo, int MODE, int TERMS, int T>
+inline hipError_t launch_coop_block(const ChainConsts<Topo::J>& cc, const SwarmIO& io, hipStream_t stream)
+{
+    static ResidencyCache cache;  // (one per kernel instantiation)
+    return launch_coop_fitted(cache, &k_swarm_coop<Topo, MODE, TERMS, T>, T,
+                              kCoopMinWaves<Topo::D, T, TERMS> / (T >= 256 ? T / 256 : 1), cc, io, stream);
 }
 
 // ------------------------------------------------ latency variant, generator split
@@ -724,20 +731,9 @@ __global__ void __launch_bounds__(2 * kCoopLatencyThreads) k_swarm_coop_split(co
 template <class Topo, int MODE, int TERMS>
 inline hipError_t launch_coop_split(const ChainConsts<Topo::J>& cc, const SwarmIO& io, hipStream_t stream)
 {
-    const auto kernel = &k_swarm_coop_split<Topo, MODE, TERMS>;
-    constexpr int T = 2 * kCoopLatencyThreads;
-    static ResidencyCache cache;
-    int cus = 0, per_cu = 0;
-    const hipError_t e = coop_residency(cache, kernel, T, &cus, &per_cu);
-    if (e != hipSuccess) return e;
-    if (per_cu < 1) return hipErrorCooperativeLaunchTooLarge;
-    SwarmIO run = io;
-    const int ng_fit = io.coop_linear ? cus / io.coop_g : (int)(((int64_t)cus / io.coop_g) & ~int64_t(7));
-    if (ng_fit < (io.coop_linear ? 1 : 8)) return hipErrorCooperativeLaunchTooLarge;
-    if (run.coop_ng > ng_fit) run.coop_ng = ng_fit;
-    const int64_t grid = (int64_t)run.coop_ng * run.coop_g;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(T), 0, stream, cc, run);
-    return hipGetLastError();
+    static ResidencyCache cache;  // (one per kernel instantiation)
+    return launch_coop_fitted(cache, &k_swarm_coop_split<Topo, MODE, TERMS>, 2 * kCoopLatencyThreads, 1, cc, io,
+                              stream);
 }
 
 template <class Topo, int MODE, int TERMS>

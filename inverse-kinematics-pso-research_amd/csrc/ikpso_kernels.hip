@@ -84,30 +84,32 @@ std::string kernel_name(const ChainHost& ch, int family)
     return std::string(fam) + "<" + topo + ">";
 }
 
+// f(topology) of the chain's compiled topology; a chain without one is an invalid value.
+template <class F>
+static hipError_t launch_on_topology(const ChainHost& ch, F&& f)
+{
+    hipError_t err = hipErrorInvalidValue;
+    const bool ok = visit_topology(ch, [&](auto topo) { err = f(topo); });
+    return ok ? err : hipErrorInvalidValue;
+}
+
 hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)
 {
     if (io.num_swarms <= 0) return hipSuccess;
     if (!ch.aux_dev) return hipErrorInvalidValue;  // the kernels read aux for the optional terms
     const int block = ((io.P + 63) / 64) * 64;
-    hipError_t err = hipErrorInvalidValue;
-    const bool ok = visit_topology(ch, [&](auto topo) {
+    return launch_on_topology(ch, [&](auto topo) {
         using T = decltype(topo);
-        err = io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
-                            : TopoOps<T>::resident(ch, mode, io, block, stream);
+        return io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
+                             : TopoOps<T>::resident(ch, mode, io, block, stream);
     });
-    return ok ? err : hipErrorInvalidValue;
 }
 
 hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipStream_t stream)
 {
     if (io.n <= 0) return hipSuccess;
     if (!ch.aux_dev) return hipErrorInvalidValue;
-    hipError_t err = hipErrorInvalidValue;
-    const bool ok = visit_topology(ch, [&](auto topo) {
-        using T = decltype(topo);
-        err = TopoOps<T>::evaluate(ch, mode, io, stream);
-    });
-    return ok ? err : hipErrorInvalidValue;
+    return launch_on_topology(ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate(ch, mode, io, stream); });
 }
 
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)
@@ -116,13 +118,12 @@ hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStre
     if (!ch.aux_dev || io.coop_g <= 0 || io.coop_ng <= 0 || (!io.coop_linear && io.coop_ng % 8 != 0) ||
         !io.coop_slots || !io.coop_error)
         return hipErrorInvalidValue;
-    hipError_t err = hipErrorInvalidValue;
-    const bool ok = visit_topology(ch, [&](auto topo) {
+    return launch_on_topology(ch, [&](auto topo) {
         using T = decltype(topo);
-        if (io.coop_g * kCoopThreads<T::D>() < io.P || io.coop_g > 64) return;  // G chunks must cover the swarm
-        err = TopoOps<T>::coop(ch, mode, io, stream);
+        // G chunks must cover the swarm
+        if (io.coop_g * kCoopThreads<T::D>() < io.P || io.coop_g > 64) return hipErrorInvalidValue;
+        return TopoOps<T>::coop(ch, mode, io, stream);
     });
-    return ok ? err : hipErrorInvalidValue;
 }
 
 // Cooperative workgroups per CU: one for short chains (the kernel's LDS block is
@@ -183,12 +184,8 @@ hipError_t launch_stream(const ChainHost& ch, int mode, const StreamIO& io, int 
 {
     if (io.num_swarms <= 0) return hipSuccess;
     if (!ch.aux_dev || io.C != (io.P + kStreamChunk - 1) / kStreamChunk) return hipErrorInvalidValue;
-    hipError_t err = hipErrorInvalidValue;
-    const bool ok = visit_topology(ch, [&](auto topo) {
-        using T = decltype(topo);
-        err = TopoOps<T>::stream(ch, mode, io, iterations, stream);
-    });
-    return ok ? err : hipErrorInvalidValue;
+    return launch_on_topology(
+        ch, [&](auto topo) { return TopoOps<decltype(topo)>::stream(ch, mode, io, iterations, stream); });
 }
 
 // Workspace bytes for B swarms of P particles and D angles (state excluded when
@@ -206,6 +203,5 @@ size_t stream_workspace_bytes(int64_t B, int P, int D, bool with_state)
     n += sizeof(int32_t) * B;                             // iteration counts (solve_batch_until)
     return n + 9 * 256;                                   // alignment slack
 }
-
 
 }  // namespace ikpso

@@ -89,6 +89,17 @@ struct PbLane {
     }
 };
 
+// The clamp after an update of dimension d: the chain's one pair of bounds
+// (kTermUniformBounds builds), or the staged per-dimension bounds.
+template <int MODE, int TERMS, class Topo>
+__device__ __forceinline__ float clamp_angle(const ChainConsts<Topo::J>& cc, const SwarmShared<Topo>& sh, int d, float x)
+{
+    if constexpr (TERMS & kTermUniformBounds)
+        return clamp_mode<MODE, true>(x, uniform_lo<TERMS>(cc), uniform_hi<TERMS>(cc));
+    else
+        return clamp_mode<MODE>(x, sh.lo[d], sh.hi[d]);
+}
+
 // One PSO iteration of one particle (lane `tid`) of a swarm whose local bests
 // sit in LDS as s_pb[d * BLOCK + lane] (shared by the resident and cooperative
 // kernels).  simulateParticlesKernel (src/kernel.cu:153-189) + calculateDistance
@@ -112,10 +123,7 @@ __device__ __forceinline__ void update_node(const ChainConsts<Topo::J>& cc, cons
         const int d = A * (k - 1) + ax;
         if (kMasked<Topo, TERMS> && !dim_free(cc, d)) continue;  // locked: stays at rest
         pso_update<MODE>(x[d], v[d], s_pb[pbl.at(d)], sh.g[d], coef, rng);
-        if constexpr (TERMS & kTermUniformBounds)
-            x[d] = clamp_mode<MODE, true>(x[d], uniform_lo<TERMS>(cc), uniform_hi<TERMS>(cc));
-        else
-            x[d] = clamp_mode<MODE>(x[d], sh.lo[d], sh.hi[d]);
+        x[d] = clamp_angle<MODE, TERMS>(cc, sh, d, x[d]);
     }
 }
 
@@ -204,10 +212,7 @@ __device__ __forceinline__ void swarm_step_tip(const ChainConsts<Topo::J>& cc, S
                 pso_update_ahead(x[d], v[d], cg[ax], pa[d], pc[d]);
             else
                 pso_update<MODE, true>(x[d], v[d], cpb[ax], cg[ax], coef, rng);
-            if constexpr (TERMS & kTermUniformBounds)
-                x[d] = clamp_mode<MODE, true>(x[d], uniform_lo<TERMS>(cc), uniform_hi<TERMS>(cc));
-            else
-                x[d] = clamp_mode<MODE>(x[d], sh.lo[d], sh.hi[d]);
+            x[d] = clamp_angle<MODE, TERMS>(cc, sh, d, x[d]);
         }
         acc.angles(k, x + A * (k - 1), crest);
         __builtin_amdgcn_sched_barrier(0);
@@ -359,10 +364,7 @@ __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, Swarm
             } else {
                 pso_update<MODE>(x[d], v[d], cpb[ax], cg[ax], coef, rng);
             }
-            if constexpr (TERMS & kTermUniformBounds)
-                x[d] = clamp_mode<MODE, true>(x[d], uniform_lo<TERMS>(cc), uniform_hi<TERMS>(cc));
-            else
-                x[d] = clamp_mode<MODE>(x[d], sh.lo[d], sh.hi[d]);
+            x[d] = clamp_angle<MODE, TERMS>(cc, sh, d, x[d]);
         }
         acc.node(cc, k, x + A * (k - 1), crest, ctgt, nullptr);
         if (!Topo::kDH) __builtin_amdgcn_sched_barrier(0);

@@ -104,6 +104,30 @@ __device__ __forceinline__ void stream_carry_chunk(const StreamIO& io, int64_t b
     for (int d = threadIdx.x; d < D; d += blockDim.x) io.pvec[to * D + d] = io.pvec[from * D + d];
 }
 
+// The streaming kernels' generator state between launches: SoA, word w of state k (of n) at
+// rng[w * n + k], so a wave's loads and stores of a word are coalesced.
+template <class Rng>
+__device__ __forceinline__ void load_rng_soa(Rng& r, const uint32_t* rng, int64_t n, int64_t k)
+{
+    r.d = rng[0 * n + k];
+    r.v0 = rng[1 * n + k];
+    r.v1 = rng[2 * n + k];
+    r.v2 = rng[3 * n + k];
+    r.v3 = rng[4 * n + k];
+    r.v4 = rng[5 * n + k];
+}
+
+template <class Rng>
+__device__ __forceinline__ void store_rng_soa(const Rng& r, uint32_t* rng, int64_t n, int64_t k)
+{
+    rng[0 * n + k] = r.d;
+    rng[1 * n + k] = r.v0;
+    rng[2 * n + k] = r.v1;
+    rng[3 * n + k] = r.v2;
+    rng[4 * n + k] = r.v3;
+    rng[5 * n + k] = r.v4;
+}
+
 template <class Topo, int MODE, int TERMS>
 __global__ void __launch_bounds__(kStreamChunk) k_stream_init(const ChainConsts<Topo::J> cc, const StreamIO io)
 {
@@ -136,13 +160,7 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_init(const ChainConsts<
         }
         pbf = fitness<Topo, MODE, TERMS>(cc, x, sh.rest, sh.tgt, nullptr, sh.dh, sh.soft);
         io.pbf[b * P + i] = pbf;
-        const int64_t n = io.num_swarms * P, k = b * P + i;
-        io.rng[0 * n + k] = rng.d;
-        io.rng[1 * n + k] = rng.v0;
-        io.rng[2 * n + k] = rng.v1;
-        io.rng[3 * n + k] = rng.v2;
-        io.rng[4 * n + k] = rng.v3;
-        io.rng[5 * n + k] = rng.v4;
+        store_rng_soa(rng, io.rng, io.num_swarms * P, b * P + i);
     }
     stream_publish_chunk<Topo>(io, b, c, sh, active ? ordered_key(pbf) : 0xFFFFFFFFu, pl);
     if (c == 0 && threadIdx.x == 0) {
@@ -175,12 +193,7 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_step(const ChainConsts<
     if (active) {
         const int64_t n = io.num_swarms * P, k = b * P + i;
         RngFor<TERMS> rng;
-        rng.d = io.rng[0 * n + k];
-        rng.v0 = io.rng[1 * n + k];
-        rng.v1 = io.rng[2 * n + k];
-        rng.v2 = io.rng[3 * n + k];
-        rng.v3 = io.rng[4 * n + k];
-        rng.v4 = io.rng[5 * n + k];
+        load_rng_soa(rng, io.rng, n, k);
         pbf = io.pbf[b * P + i];
         // One node at a time: update its three angles (simulateParticlesKernel,
         // src/kernel.cu:153-189: draws r1, r2, r3 per dimension in dimension
@@ -279,12 +292,7 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_step(const ChainConsts<
                 pl.st(2, d, imp ? xn : po);
             }
         }
-        io.rng[0 * n + k] = rng.d;
-        io.rng[1 * n + k] = rng.v0;
-        io.rng[2 * n + k] = rng.v1;
-        io.rng[3 * n + k] = rng.v2;
-        io.rng[4 * n + k] = rng.v3;
-        io.rng[5 * n + k] = rng.v4;
+        store_rng_soa(rng, io.rng, n, k);
     }
     stream_publish_chunk<Topo>(io, b, c, sh, active ? ordered_key(pbf) : 0xFFFFFFFFu, pl);
 }
@@ -318,12 +326,7 @@ __global__ void __launch_bounds__(kStreamChunk) k_stream_finalize(const ChainCon
     if (i < io.P) {  // generator states back to the caller's / solver's layout
         const int64_t n = io.num_swarms * P, k = b * P + i;
         Xorwow rng;
-        rng.d = io.rng[0 * n + k];
-        rng.v0 = io.rng[1 * n + k];
-        rng.v1 = io.rng[2 * n + k];
-        rng.v2 = io.rng[3 * n + k];
-        rng.v3 = io.rng[4 * n + k];
-        rng.v4 = io.rng[5 * n + k];
+        load_rng_soa(rng, io.rng, n, k);
         store_rng(rng, io.rng_aos + k);
     }
 }
@@ -347,7 +350,10 @@ inline hipError_t run_stream(const ChainHost& ch, StreamIO io, int iterations, h
 template <class Topo, int MODE>
 inline hipError_t run_stream_terms(const ChainHost& ch, const StreamIO& io, int iterations, hipStream_t stream)
 {
-    // Same term specialisation as run_resident.
+    // run_resident's term specialisation without its revolution-unit builds: the
+    // streaming kernels keep their angles in radians, so the folded chain's builds and the two
+    // hot FAST term sets are taken as they are, and there are no builds for the reference
+    // scene's unit limits, config 5's symmetric soft limits or the uniform-bounds collider scene.
     const int terms = term_set(ch);
     hipError_t err = hipSuccess;
     if (dh_terms<Topo>(terms, &err,

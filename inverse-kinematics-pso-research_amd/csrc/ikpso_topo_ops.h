@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "ikpso_kernels.h"
 
 namespace ikpso {
@@ -30,47 +32,35 @@ struct TrackOps {
 template <class Topo>
 struct TopoOps {
     static constexpr bool kRef = !Topo::kDH;
-    using Ref = ModeOps<Topo, IKPSO_ARITH_REFERENCE>;
-    using Fast = ModeOps<Topo, IKPSO_ARITH_FAST>;
-    static hipError_t resident(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    // f(mode as a compile-time constant) for the arithmetic mode `mode`
+    template <class F>
+    static hipError_t with_mode(int mode, F&& f)
     {
         if (mode == IKPSO_ARITH_REFERENCE) {
-            if constexpr (kRef) return Ref::resident(ch, io, block, s);
+            if constexpr (kRef) return f(std::integral_constant<int, IKPSO_ARITH_REFERENCE>{});
             return hipErrorNotSupported;
         }
-        return Fast::resident(ch, io, block, s);
+        return f(std::integral_constant<int, IKPSO_ARITH_FAST>{});
+    }
+    static hipError_t resident(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    {
+        return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::resident(ch, io, block, s); });
     }
     static hipError_t track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
     {
-        if (mode == IKPSO_ARITH_REFERENCE) {
-            if constexpr (kRef) return TrackOps<Topo, IKPSO_ARITH_REFERENCE>::resident(ch, io, block, s);
-            return hipErrorNotSupported;
-        }
-        return TrackOps<Topo, IKPSO_ARITH_FAST>::resident(ch, io, block, s);
+        return with_mode(mode, [&](auto m) { return TrackOps<Topo, decltype(m)::value>::resident(ch, io, block, s); });
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {
-        if (mode == IKPSO_ARITH_REFERENCE) {
-            if constexpr (kRef) return Ref::stream(ch, io, iterations, s);
-            return hipErrorNotSupported;
-        }
-        return Fast::stream(ch, io, iterations, s);
+        return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::stream(ch, io, iterations, s); });
     }
     static hipError_t evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipStream_t s)
     {
-        if (mode == IKPSO_ARITH_REFERENCE) {
-            if constexpr (kRef) return Ref::evaluate(ch, io, s);
-            return hipErrorNotSupported;
-        }
-        return Fast::evaluate(ch, io, s);
+        return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
     static hipError_t coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t s)
     {
-        if (mode == IKPSO_ARITH_REFERENCE) {
-            if constexpr (kRef) return Ref::coop(ch, io, s);
-            return hipErrorNotSupported;
-        }
-        return Fast::coop(ch, io, s);
+        return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::coop(ch, io, s); });
     }
 };
 
