@@ -53,7 +53,8 @@ typedef struct ikpso_node {
     float min_rotation[3];
     float length;
     float target_position[3]; /* effectors only */
-    float target_rotation[3]; /* unused by the fitness (as in the reference) */
+    float target_rotation[3]; /* unused by the fitness (as in the reference); orientation targets are
+                                 an argument of ikpso_solve_track_pose */
 } ikpso_node;
 
 /* XORWOW generator state with cuRAND's curandStateXORWOW layout (48 bytes),
@@ -287,6 +288,50 @@ ikpso_status ikpso_solve_track(ikpso_solver* solver, const float* targets, const
                                int64_t num_swarms, int32_t frames, int32_t max_iterations, float stop_fitness,
                                float* out_angles, float* out_fitness, float* out_residual,
                                int32_t* out_iterations, void* stream);
+
+/* Pose targets: ikpso_solve_track with a tip orientation term (added after ABI 5;
+ * detect by symbol).  Every fitness of the call -- the local and global bests, the
+ * per-frame stop test, out_fitness -- is ikpso_solve_track's plus, added last,
+ *   effector_weight[tip] * orientation_weight * |R_eff - R_target|_F^2
+ * where R_eff is the world rotation of the EFFECTOR NODE's frame as the Euler chain
+ * defines it (the origin's Rx Ry Rz, then Rx Ry Rz of every node down to the
+ * effector, locked axes at their rotation[]; the link translation does not turn the
+ * frame) and R_target the caller's rotation.  The squared Frobenius distance is
+ * 4 (1 - cos theta) for the geodesic angle theta between the two.  A DH arm's tool
+ * frame differs from the node frame by a constant rotation (ikpso.dh.DHArm
+ * .tool_rotation; node_target converts).
+ *   target_rot          device, [T][B][9]: row-major 3x3 rotations, time-major like
+ *                       targets; may be NULL when orientation_weight == 0.
+ *   orientation_weight  >= 0.  With 0 every output, iteration count and generator
+ *                       state equals ikpso_solve_track's, bit for bit (the term is
+ *                       absent, and the call runs the track kernel without it; the
+ *                       kernels with the term evaluate the position term by the
+ *                       same expressions, whose FMA contraction may differ by an
+ *                       ulp from kernel to kernel, as between any two FAST builds).
+ * Every other argument, and the contract (a fresh swarm per frame warm-started from
+ * the previous answer; the per-frame early stop on the whole fitness, this term
+ * included; frames == 1 is the pose form of solve_batch_until, a negative
+ * stop_fitness that of solve_batch), are ikpso_solve_track's.  out_residual stays
+ * the positional checkDistance residual.  A particle draws D + 3 D n values, as
+ * without the term.
+ * IKPSO_ERR_INVALID_ARG: a NaN or negative orientation_weight, a NaN stop_fitness,
+ * frames > 0 with a NULL targets or out_angles, orientation_weight > 0 with a NULL
+ * target_rot.
+ * IKPSO_ERR_UNSUPPORTED: only the folded chain's resident track kernels have the
+ * term, and no kernel without it is ever run in their place.  So every solver but
+ * a FAST one of a masked serial chain with a tip effector that folds (see
+ * axis_mask), created on the resident family with a swarm that fits one
+ * workgroup, is refused: REFERENCE arithmetic, IKPSO_FLAG_NO_FOLD, an unmasked
+ * chain, a tree, a chain with a distance or collider term, a streaming or
+ * cooperative solver (requested, or picked by AUTO for a swarm above one
+ * workgroup).  The refusal comes before the frames == 0 / num_swarms == 0 return
+ * (IKPSO_OK, no device work).
+ * ikpso_solver_evaluate is unchanged: its fitness never includes this term. */
+ikpso_status ikpso_solve_track_pose(ikpso_solver* solver, const float* targets, const float* target_rot,
+                                    float orientation_weight, const float* start_pose, int64_t num_swarms,
+                                    int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
+                                    float* out_fitness, float* out_residual, int32_t* out_iterations,
+                                    void* stream);
 
 /* Settle the last solve_batch (ABI >= 3).  After a cooperative-family solve:
  * wait for it and, if a group gave up (the GPU shared with other work), restore

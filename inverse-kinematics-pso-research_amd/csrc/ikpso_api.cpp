@@ -429,6 +429,10 @@ struct SolveArgs {
     uint32_t stop_key = 0;              // ikpso_solve_batch_until (0: no stop)
     int32_t* out_iterations = nullptr;
     int32_t frames = 0;  // > 0: ikpso_solve_track, every buffer but start_pose time-major
+    // ikpso_solve_track_pose: the pose track kernels, with the orientation targets [frames][B][9]
+    bool pose = false;
+    const float* target_rot = nullptr;
+    float orientation_weight = 0.0f;
 };
 
 // The kernels the last solve ran, for ikpso_solver_kernel_name.
@@ -515,6 +519,10 @@ SwarmIO swarm_io(const ikpso_solver* s, const SolveArgs& a)
     io.num_swarms = a.num_swarms;
     io.stop_key = a.stop_key;
     io.out_iterations = a.out_iterations;
+    io.pose = a.pose ? 1 : 0;
+    io.target_rot = a.target_rot;
+    io.orient_w = a.orientation_weight;
+    for (int i = 0; i < 9; ++i) io.tip_rot[i] = s->solve_chain().tip_rot[i];
     return io;
 }
 
@@ -906,6 +914,34 @@ ikpso_status ikpso_solve_track(ikpso_solver* s, const float* targets, const floa
         st = solve_streaming(s, a, hs);
     }
     return st;
+}
+
+// ikpso_solve_track on the folded chain's pose kernels: the same frame loop in one launch, the
+// orientation term in every fitness.  No other kernel has the term, so no other solver is served.
+ikpso_status ikpso_solve_track_pose(ikpso_solver* s, const float* targets, const float* target_rot,
+                                    float orientation_weight, const float* start_pose, int64_t num_swarms,
+                                    int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
+                                    float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
+{
+    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
+        return IKPSO_ERR_INVALID_ARG;
+    if (!(orientation_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
+    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
+    if (orientation_weight > 0.0f && !target_rot) return IKPSO_ERR_INVALID_ARG;
+    if (!s->use_dh || s->family != IKPSO_KERNEL_RESIDENT) return IKPSO_ERR_UNSUPPORTED;
+    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
+    const ikpso_status st = begin_solve(s, num_swarms, true);
+    if (st != IKPSO_OK) return st;
+    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
+                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
+    // Weight 0 is the term absent: the plain track kernel computes that fitness, and only it gives
+    // ikpso_solve_track's bits.  A pose kernel evaluates the same position expressions, but the compiler
+    // contracts an a*b + c*d of them into an FMA the other way round here and there (the kernels'
+    // contraction is not pinned), an ulp away.
+    a.pose = orientation_weight > 0.0f;
+    a.target_rot = target_rot;
+    a.orientation_weight = orientation_weight;
+    return solve_resident(s, a, (hipStream_t)stream);
 }
 
 // ordered_key_host / key_to_float, for the tests (not part of the declared ABI)

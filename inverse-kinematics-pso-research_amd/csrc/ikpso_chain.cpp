@@ -478,6 +478,8 @@ bool build_dh(const std::vector<ikpso_node>& nodes, const ChainHost& eu, const E
         for (int r = 0; r < 3; ++r) dc[12 * j + 9 + r] = (float)S[j][r];
     }
     for (int r = 0; r < 3; ++r) dc[12 * N + r] = (float)q0[r];
+    for (int r = 0; r < 3; ++r)  // what the loop left in g: G (ChainHost::tip_rot)
+        for (int c = 0; c < 3; ++c) dh.tip_rot[3 * r + c] = (float)g.m[r][c];
     return chain_supported(dh);
 }
 

@@ -597,7 +597,7 @@ __device__ __forceinline__ Frame child_frame(const Frame& P, float a, float b, f
 // and cooperative FAST builds with the hardware sin/cos (the streaming kernels
 // keep the reference's radian layout in HBM).
 constexpr int kTermPosRef = 1, kTermPenalty = 2, kTermRuntime = 4, kTermUniformBounds = 8, kTermColliders = 16,
-              kTermMask = 32, kTermRev = 64, kTermUnitBounds = 128, kTermSymPenalty = 256;
+              kTermMask = 32, kTermRev = 64, kTermUnitBounds = 128, kTermSymPenalty = 256, kTermOrient = 512;
 // kTermUnitBounds (with kTermRev and kTermUniformBounds): the clamp bounds are
 // exactly [0, 1] revolutions -- the reference scene's [0, 2pi] -- so the clamp
 // is the VALU's free output clamp on the position update instead of a v_med3
@@ -607,6 +607,8 @@ constexpr int kTermPosRef = 1, kTermPenalty = 2, kTermRuntime = 4, kTermUniformB
 // revolution of them, so the penalty's overshoot max(|x| - h, 0) is the VALU's
 // free output clamp of |x| - h (<= 1) instead of two subtractions and a v_max3
 // (half rate): BASELINE config 5's +-pi/2 soft limits inside +-pi.
+// kTermOrient (the folded chain's track kernels, ikpso_solve_track_pose): the tip orientation
+// term w |R_eff - R_target|_F^2, added last (TipBackAccDH).
 
 // Parity-attribution builds of FAST arithmetic (tools/tier_b_attribution.py; built into
 // variants/, never shipped): each switch removes one FAST ingredient --
@@ -1123,7 +1125,10 @@ struct TipBackAcc {
     const float* soft;
     float rot_diff, pen, ux, uy, uz;
 
-    __device__ __forceinline__ TipBackAcc(const float*, const float* soft_) : soft(soft_), rot_diff(0.0f), pen(0.0f) {}
+    __device__ __forceinline__ TipBackAcc(const float*, const float* soft_, const float* = nullptr)
+        : soft(soft_), rot_diff(0.0f), pen(0.0f)
+    {
+    }
 
     // node k's angle terms (node order, as FitnessAcc::terms)
     __device__ __forceinline__ void angles(int k, const float* ang, const float* rest3)
@@ -1197,10 +1202,16 @@ struct TipBackAccDH {
     static constexpr int HW = kHwTrig<Topo, MODE, TERMS>;
     const float* dhc;
     const float* soft;
+    // kTermOrient: PoseTarget::v of the swarm's frame -- T' = R_target G^T (9, row-major), then the weight
+    const float* pose;
     float rot_diff, pen, ux, uy, uz;
+    // kTermOrient: the x and y columns of the rotation C_k Rz(t_k) ... C_J Rz(t_J), carried from the tip
+    // back beside u through the same constants (13 multiply-adds per column and joint; the z column is
+    // their cross product, in finish).  After joint 1 they are columns of W_J Rz(t_J) = R_eff G^T.
+    float ax, ay, az, bx, by, bz;
 
-    __device__ __forceinline__ TipBackAccDH(const float* dh, const float* soft_)
-        : dhc(dh), soft(soft_), rot_diff(0.0f), pen(0.0f)
+    __device__ __forceinline__ TipBackAccDH(const float* dh, const float* soft_, const float* pose_ = nullptr)
+        : dhc(dh), soft(soft_), pose(pose_), rot_diff(0.0f), pen(0.0f)
     {
     }
 
@@ -1231,6 +1242,21 @@ struct TipBackAccDH {
         ux = C[0] * r0 + C[1] * r1 + C[2] * w2;
         uy = C[3] * r0 + C[4] * r1 + C[5] * w2;
         uz = C[6] * r0 + C[7] * r1 + C[8] * w2;
+        if constexpr (TERMS & kTermOrient) {
+            if (k == J) {  // C_J Rz(t_J) (e_x, e_y)
+                ax = C[0] * ct + C[1] * st, ay = C[3] * ct + C[4] * st, az = C[6] * ct + C[7] * st;
+                bx = C[1] * ct - C[0] * st, by = C[4] * ct - C[3] * st, bz = C[7] * ct - C[6] * st;
+            } else {
+                const float a0 = ct * ax - st * ay, a1 = st * ax + ct * ay, a2 = az;
+                const float b0 = ct * bx - st * by, b1 = st * bx + ct * by, b2 = bz;
+                ax = C[0] * a0 + C[1] * a1 + C[2] * a2;
+                ay = C[3] * a0 + C[4] * a1 + C[5] * a2;
+                az = C[6] * a0 + C[7] * a1 + C[8] * a2;
+                bx = C[0] * b0 + C[1] * b1 + C[2] * b2;
+                by = C[3] * b0 + C[4] * b1 + C[5] * b2;
+                bz = C[6] * b0 + C[7] * b1 + C[8] * b2;
+            }
+        }
     }
 
     __device__ __forceinline__ float finish(const ChainConsts<J>& cc, const float* tgt3) const
@@ -1240,6 +1266,17 @@ struct TipBackAccDH {
         const float distance = ((ex * ex + ey * ey) + ez * ez) * cc.eff_w[J];
         float f = distance + angle_weight<TERMS>(cc) * rot_diff;
         if constexpr (TERMS & kTermPenalty) f = f + limit_weight<TERMS>(cc) * pen;
+        if constexpr (TERMS & kTermOrient) {
+            // |W_J Rz(t_J) - T'|_F^2 = |R_eff - R_target|_F^2 (a right rotation keeps the norm): nine
+            // squared differences, column by column; weight 0 adds an exact +0
+            const float cx = ay * bz - az * by, cy = az * bx - ax * bz, cz = ax * by - ay * bx;
+            const float d0 = ax - pose[0], d1 = bx - pose[1], d2 = cx - pose[2];
+            const float d3 = ay - pose[3], d4 = by - pose[4], d5 = cy - pose[5];
+            const float d6 = az - pose[6], d7 = bz - pose[7], d8 = cz - pose[8];
+            const float orient = ((d0 * d0 + d3 * d3) + d6 * d6) + ((d1 * d1 + d4 * d4) + d7 * d7) +
+                                 ((d2 * d2 + d5 * d5) + d8 * d8);
+            f = f + pose[9] * orient;
+        }
         return f;
     }
 };
@@ -1253,14 +1290,16 @@ using TipAccFor =
 template <class Topo, int MODE, int TERMS>
 __device__ __forceinline__ float fitness(const ChainConsts<Topo::J>& cc, const float* x, const float* rest,
                                          const float* tgt, float* node_pos /* [3J] or nullptr */,
-                                         const float* dhc, const float* soft)
+                                         const float* dhc, const float* soft, const float* pose = nullptr)
 {
+    static_assert(!(TERMS & kTermOrient) || (Topo::kDH && kTipBackward<Topo, MODE, TERMS>),
+                  "the orientation term: the folded chain's tip-backward builds");
     constexpr int A = Topo::A;
     if constexpr (kTipBackward<Topo, MODE, TERMS>) {
         if (!node_pos) {
             constexpr int J = Topo::J;
             using Acc = TipAccFor<Topo, MODE, TERMS>;
-            Acc tb(dhc, soft);
+            Acc tb(dhc, soft, pose);
 #pragma unroll
             for (int k = 1; k <= J; ++k) tb.angles(k, x + A * (k - 1), rest + A * (k - 1));
 #pragma unroll

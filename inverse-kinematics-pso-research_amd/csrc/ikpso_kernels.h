@@ -84,6 +84,10 @@ struct ChainHost {
     // solves take the polynomial sin/cos (the collider builds, with no collider)
     bool poly_trig = false;
     size_t dh_off = 0;            // TopoDH constants in aux (ChainConsts::dh_off), 12 J + 4 floats
+    // TopoDH: the constant rotation G after the last free axis (that axis's permutation transposed, times
+    // the locked rotations down to the effector), row-major, rounded once from fp64: the effector node's
+    // world rotation is R_eff = W_J Rz(t_J) G.  Read by the pose track kernels alone (SwarmIO::tip_rot).
+    float tip_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     int dof() const { return dfree; }
     int kernel_dims() const { return topo == TopoKind::DH ? J : 3 * J; }
 };

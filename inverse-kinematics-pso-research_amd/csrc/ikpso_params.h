@@ -108,6 +108,14 @@ struct SwarmIO {
     // time-major ([frames][B]...), start_pose is frame 0's.  0: the plain and stopping kernels,
     // which never read it.
     int32_t frames;
+    // Pose track kernels only (ikpso_solve_track_pose; kTermOrient): pose != 0 routes the launch to
+    // them.  target_rot: [frames][B][9] row-major rotations, or null with a zero weight; tip_rot: the
+    // folded chain's constant G with R_eff = W_J Rz(t_J) G (ChainHost::tip_rot).  Last, so that the
+    // fields above keep their kernarg offsets.
+    int32_t pose;
+    float orient_w;
+    const float* target_rot;
+    float tip_rot[9];
 };
 
 // Streaming (state-in-HBM) kernels: one launch per PSO iteration over every

@@ -99,6 +99,31 @@ __device__ __forceinline__ void stage_swarm_targets(const ChainConsts<Topo::J>& 
     }
 }
 
+// The pose track kernels' extra LDS (SwarmLds::Extra; kTermOrient): the orientation target of the
+// swarm's current frame, T' = R_target G^T row-major in v[0..8], and the term's weight
+// eff_w[tip] * orientation_weight in v[9].  No other build has it.
+struct PoseTarget {
+    float v[16];
+};
+
+// T' of one (frame, swarm) cell, formed once by thread 0 (constant indices into the kernarg's G);
+// the caller barriers.  A null target_rot (weight 0) stages zeros.
+template <class Topo>
+__device__ __forceinline__ void stage_swarm_orientation(const ChainConsts<Topo::J>& cc, const SwarmIO& io,
+                                                        int64_t cell, float* pose)
+{
+    if (threadIdx.x != 0) return;
+    const float* r = io.target_rot ? io.target_rot + cell * 9 : nullptr;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float r0 = r ? r[3 * i] : 0.0f, r1 = r ? r[3 * i + 1] : 0.0f, r2 = r ? r[3 * i + 2] : 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            pose[3 * i + c] = r0 * io.tip_rot[3 * c] + r1 * io.tip_rot[3 * c + 1] + r2 * io.tip_rot[3 * c + 2];
+    }
+    pose[9] = cc.eff_w[Topo::J] * io.orient_w;
+}
+
 // The uniforms that depend on the chain alone: folded-chain constants, soft limits and the
 // near-collider table.
 template <class Topo, int TERMS = 0>

@@ -27,6 +27,13 @@ struct TrackOps {
     static hipError_t resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
+// The folded chain's pose track kernels (ikpso_solve_track_pose; TopoDH only, FAST), in units of
+// their own again (ikpso_inst_pose_dh_*.hip).
+template <class Topo>
+struct PoseOps {
+    static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -49,6 +56,13 @@ struct TopoOps {
     static hipError_t track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
     {
         return with_mode(mode, [&](auto m) { return TrackOps<Topo, decltype(m)::value>::resident(ch, io, block, s); });
+    }
+    static hipError_t pose_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    {
+        if constexpr (Topo::kDH) {
+            if (mode == IKPSO_ARITH_FAST) return PoseOps<Topo>::track(ch, io, block, s);
+        }
+        return hipErrorNotSupported;  // no other kernel has the orientation term
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {

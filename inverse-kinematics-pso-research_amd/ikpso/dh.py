@@ -93,17 +93,34 @@ def dh_forward(theta: Sequence[float], d, a, alpha, base: Optional[np.ndarray] =
     return m[:3, 3]
 
 
+def dh_forward_pose(theta: Sequence[float], d, a, alpha, base: Optional[np.ndarray] = None) -> np.ndarray:
+    """Tool frame of a standard DH arm (float64 4x4), the textbook product; its translation is
+    dh_forward's."""
+    m = np.eye(4) if base is None else np.asarray(base, dtype=np.float64)
+    for t, di, ai, al in zip(theta, d, a, alpha):
+        m = m @ dh_matrix(t, di, ai, al)
+    return m
+
+
 @dataclass
 class DHArm:
     """A DH arm built as a reference node tree.  `origin` is the tree's root
     (marshal it with origin.to_cuda()); `joint_nodes[i]` carries theta_i in its
-    z angle, offset by `z_offset[i]`; `tool` is the effector node."""
+    z angle, offset by `z_offset[i]`; `tool` is the effector node.  `tool_rotation` is the
+    constant K with (DH tool frame) = (effector node frame) K: Rx(alpha_n), preceded by Ry(-beta)
+    when the last joint has d != 0 (the fixed rotation a further joint would have carried in)."""
 
     origin: OriginNode
     joint_nodes: List[Node]
     z_offset: np.ndarray
     tool: EffectorNode
     target: TargetNode
+    tool_rotation: np.ndarray = None
+
+    def node_target(self, r_tool: np.ndarray) -> np.ndarray:
+        """Effector-node orientation(s) [..., 3, 3] whose DH tool frame is r_tool: the orientation
+        targets of solve_track / solve_until are measured in the effector node's frame."""
+        return np.asarray(r_tool, dtype=np.float64) @ self.tool_rotation.T
 
     @property
     def dof(self) -> int:
@@ -190,7 +207,7 @@ def dh_arm(a: Sequence[float], alpha: Sequence[float], d: Sequence[float], theta
             k = _ry(-beta) @ _rx(float(alpha[i]))
         else:
             k = _rx(float(alpha[i]))
-    return DHArm(origin, joints, np.asarray(offsets, dtype=np.float64), tool, tgt)
+    return DHArm(origin, joints, np.asarray(offsets, dtype=np.float64), tool, tgt, np.array(k, dtype=np.float64))
 
 
 def iiwa14(target=(0.0, 0.0, 0.0)) -> DHArm:

@@ -279,9 +279,26 @@ class BatchSolver:
             _abi.check(self._lib.ikpso_solver_sync(self._h), "ikpso_solver_sync")
         return angles, fitness, res
 
+    def _solve_pose(self, targets, target_rot, orientation_weight: float, start_pose, B: int, T: int, it: int,
+                    stop: float, outs, stream) -> None:
+        """ikpso_solve_track_pose over time-major buffers: target_rot holds T * B row-major 3x3
+        rotations of the effector node's frame."""
+        torch = _torch()
+        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        if target_rot.numel() != T * B * 9 or tuple(target_rot.shape[-2:]) != (3, 3):
+            raise ValueError(f"target_rot must hold {T * B} rotations [..., 3, 3]")
+        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (target_rot, "target_rot")):
+            self._check_tensor(t, name, dev)
+        angles, fitness, res, iters = outs
+        _abi.check(self._lib.ikpso_solve_track_pose(self._h, _dev_ptr(targets), _dev_ptr(target_rot),
+                                                    float(orientation_weight), _dev_ptr(start_pose), B, T, it, stop,
+                                                    _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
+                                                    _dev_ptr(iters), _stream_handle(stream)),
+                   "ikpso_solve_track_pose")
+
     def solve_until(self, targets=None, start_pose=None, max_iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, num_swarms: Optional[int] = None, residual: bool = True,
-                    stream=None):
+                    stream=None, target_rot=None, orientation_weight: float = 0.0):
         """solve() with a per-swarm early stop (ikpso_solve_batch_until): swarm b stops after the
         first iteration n >= 0 at which its global-best fitness is <= stop_fitness, else it runs
         max_iterations (None: the solver's PSOConfig.iterations).  stop_fitness tests the fitness,
@@ -289,7 +306,9 @@ class BatchSolver:
         never stops.  Returns (angles [B, D], fitness [B], residual [B] or None, iterations [B]
         int32) device tensors; a stopped swarm's answers and generator states are those of
         solve(iterations=n), bit for bit.  Runs the resident or the streaming kernels; a
-        kernel="coop" solver raises (unsupported configuration).  Stream-ordered, asynchronous."""
+        kernel="coop" solver raises (unsupported configuration).  Stream-ordered, asynchronous.
+        target_rot (device [B, 3, 3] float32) with orientation_weight: the pose form, one frame of
+        solve_track's (see there); it needs targets."""
         torch = _torch()
         if num_swarms is None:
             if targets is None:
@@ -307,6 +326,12 @@ class BatchSolver:
         fitness = torch.empty((B,), dtype=torch.float32, device=dev)
         res = torch.empty((B,), dtype=torch.float32, device=dev) if residual else None
         iters = torch.empty((B,), dtype=torch.int32, device=dev)
+        if target_rot is not None:
+            if targets is None:
+                raise ValueError("the pose form needs targets")
+            self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, 1, it, stop,
+                             (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
         _abi.check(self._lib.ikpso_solve_batch_until(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, it, stop,
@@ -316,7 +341,8 @@ class BatchSolver:
         return angles, fitness, res, iters
 
     def solve_track(self, targets, start_pose=None, iterations: Optional[int] = None,
-                    stop_fitness: Optional[float] = None, residual: bool = True, stream=None):
+                    stop_fitness: Optional[float] = None, residual: bool = True, stream=None, target_rot=None,
+                    orientation_weight: float = 0.0):
         """B swarms following T waypoints each (ikpso_solve_track): targets is device [T, B, E, 3],
         time-major; frame t of swarm b is solve_until on targets[t] with `iterations` as its
         maximum (None: the solver's PSOConfig.iterations), warm-started from start_pose (device
@@ -326,7 +352,15 @@ class BatchSolver:
         Returns (angles [T, B, D], fitness [T, B], residual [T, B] or None, iterations [T, B]
         int32) device tensors.  The resident family runs the whole track in one launch, the
         streaming kernels one solve per frame; a kernel="coop" solver raises (unsupported
-        configuration).  Stream-ordered, asynchronous."""
+        configuration).  Stream-ordered, asynchronous.
+        target_rot (device [T, B, 3, 3] float32, row-major rotations): pose targets
+        (ikpso_solve_track_pose).  Every fitness then carries eff_w[tip] * orientation_weight *
+        |R_eff - target_rot|_F^2, R_eff the world rotation of the effector NODE's frame (for a DH arm's
+        tool frame pass DHArm.node_target(R_tool)); the stop tests and the returned fitness include it,
+        the residual stays positional.  With weight 0 the answers equal the call without target_rot,
+        bit for bit.  Only a FAST solver of a masked serial chain that folds, on the resident
+        family, has the term; every other solver raises (unsupported configuration).  With
+        target_rot=None this is ikpso_solve_track as before."""
         torch = _torch()
         if targets is None or targets.dim() != 4:
             raise ValueError(f"targets must be [T, B, {self.effectors}, 3]")
@@ -342,6 +376,10 @@ class BatchSolver:
         fitness = torch.empty((T, B), dtype=torch.float32, device=dev)
         res = torch.empty((T, B), dtype=torch.float32, device=dev) if residual else None
         iters = torch.empty((T, B), dtype=torch.int32, device=dev)
+        if target_rot is not None:
+            self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, T, it, stop,
+                             (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
         _abi.check(self._lib.ikpso_solve_track(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, T, it, stop,
