@@ -333,6 +333,46 @@ ikpso_status ikpso_solve_track_pose(ikpso_solver* solver, const float* targets, 
                                     float* out_fitness, float* out_residual, int32_t* out_iterations,
                                     void* stream);
 
+/* Aim targets: ikpso_solve_track with a tool-axis term, the roll about the axis left
+ * free (added after ABI 5; detect by symbol).  Every fitness of the call -- the local
+ * and global bests, the per-frame stop test, out_fitness -- is ikpso_solve_track's
+ * plus, added last,
+ *   effector_weight[tip] * aim_weight * |R_eff a - d|^2
+ * where R_eff is the world rotation of the EFFECTOR NODE's frame exactly as
+ * ikpso_solve_track_pose defines it, a the caller's axis in that node frame and d the
+ * frame's world direction.  For unit vectors the value is 2 (1 - cos phi), phi the
+ * angle between the tool axis and the direction; a rotation of the tool about a does
+ * not change it, so the term takes 2 of the 3 orientation degrees of freedom.  For
+ * an axis named in a DH arm's tool frame see ikpso.dh.DHArm.node_axis.
+ *   aim_dir     device, [T][B][3], time-major like targets.  Used AS GIVEN: pass unit
+ *               vectors; a non-unit d gives the expression above and nothing else.
+ *               May be NULL when aim_weight == 0.
+ *   aim_axis    HOST memory, 3 floats, read during the call; the same for every swarm
+ *               and frame.  Finite, of norm >= 1e-6; the library normalises it (in
+ *               fp64).  May be NULL when aim_weight == 0.
+ *   aim_weight  >= 0.  With 0 the term is absent and the call runs the track kernel
+ *               without it: every output, iteration count and generator state equals
+ *               ikpso_solve_track's, bit for bit (as ikpso_solve_track_pose at
+ *               weight 0).
+ * Every other argument, and the contract (a fresh swarm per frame warm-started from
+ * the previous answer; the per-frame early stop on the whole fitness, this term
+ * included; frames == 1 is the aim form of solve_batch_until, a negative stop_fitness
+ * never stops), are ikpso_solve_track's.  out_residual stays the positional
+ * checkDistance residual.  A particle draws D + 3 D n values, as without the term.
+ * IKPSO_ERR_INVALID_ARG: a NaN or negative aim_weight, a NaN stop_fitness, frames > 0
+ * with a NULL targets or out_angles, aim_weight > 0 with a NULL aim_dir, or with a
+ * NULL, non-finite or near-zero (norm < 1e-6) aim_axis.
+ * IKPSO_ERR_UNSUPPORTED: exactly the solvers ikpso_solve_track_pose refuses (only a
+ * FAST, folded, resident solver whose swarm fits one workgroup is served), before the
+ * frames == 0 / num_swarms == 0 return (IKPSO_OK, no device work).
+ * The aim and the orientation term are not combined: a call has one or the other.
+ * ikpso_solver_evaluate is unchanged: its fitness never includes this term. */
+ikpso_status ikpso_solve_track_aim(ikpso_solver* solver, const float* targets, const float* aim_dir,
+                                   const float* aim_axis, float aim_weight, const float* start_pose,
+                                   int64_t num_swarms, int32_t frames, int32_t max_iterations,
+                                   float stop_fitness, float* out_angles, float* out_fitness,
+                                   float* out_residual, int32_t* out_iterations, void* stream);
+
 /* Settle the last solve_batch (ABI >= 3).  After a cooperative-family solve:
  * wait for it and, if a group gave up (the GPU shared with other work), restore
  * the generator states from the snapshot taken before the launch and re-run the

@@ -433,6 +433,11 @@ struct SolveArgs {
     bool pose = false;
     const float* target_rot = nullptr;
     float orientation_weight = 0.0f;
+    // ikpso_solve_track_aim: the aim track kernels, with the directions [frames][B][3] and a' = G a
+    bool aim = false;
+    const float* aim_dir = nullptr;
+    float aim_weight = 0.0f;
+    float aim_axis[3] = {0.0f, 0.0f, 0.0f};
 };
 
 // The kernels the last solve ran, for ikpso_solver_kernel_name.
@@ -523,6 +528,10 @@ SwarmIO swarm_io(const ikpso_solver* s, const SolveArgs& a)
     io.target_rot = a.target_rot;
     io.orient_w = a.orientation_weight;
     for (int i = 0; i < 9; ++i) io.tip_rot[i] = s->solve_chain().tip_rot[i];
+    io.aim = a.aim ? 1 : 0;
+    io.aim_w = a.aim_weight;
+    io.aim_dir = a.aim_dir;
+    for (int i = 0; i < 3; ++i) io.aim_axis[i] = a.aim_axis[i];
     return io;
 }
 
@@ -941,6 +950,32 @@ ikpso_status ikpso_solve_track_pose(ikpso_solver* s, const float* targets, const
     a.pose = orientation_weight > 0.0f;
     a.target_rot = target_rot;
     a.orientation_weight = orientation_weight;
+    return solve_resident(s, a, (hipStream_t)stream);
+}
+
+// ikpso_solve_track on the folded chain's aim kernels: the pose entry's routing and refusals, the
+// tool-axis term |R_eff a - d|^2 in the orientation term's place.
+ikpso_status ikpso_solve_track_aim(ikpso_solver* s, const float* targets, const float* aim_dir, const float* aim_axis,
+                                   float aim_weight, const float* start_pose, int64_t num_swarms, int32_t frames,
+                                   int32_t max_iterations, float stop_fitness, float* out_angles, float* out_fitness,
+                                   float* out_residual, int32_t* out_iterations, void* stream)
+{
+    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
+        return IKPSO_ERR_INVALID_ARG;
+    if (!(aim_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
+    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
+    if (aim_weight > 0.0f && (!aim_dir || !aim_axis)) return IKPSO_ERR_INVALID_ARG;
+    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
+                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
+    // Weight 0 is the term absent: the plain track kernel, as in ikpso_solve_track_pose
+    a.aim = aim_weight > 0.0f;
+    if (a.aim && !aim_axis_folded(s->solve_chain(), aim_axis, a.aim_axis)) return IKPSO_ERR_INVALID_ARG;
+    if (!s->use_dh || s->family != IKPSO_KERNEL_RESIDENT) return IKPSO_ERR_UNSUPPORTED;
+    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
+    const ikpso_status st = begin_solve(s, num_swarms, true);
+    if (st != IKPSO_OK) return st;
+    a.aim_dir = aim_dir;
+    a.aim_weight = aim_weight;
     return solve_resident(s, a, (hipStream_t)stream);
 }
 

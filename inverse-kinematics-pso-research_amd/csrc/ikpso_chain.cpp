@@ -483,4 +483,16 @@ bool build_dh(const std::vector<ikpso_node>& nodes, const ChainHost& eu, const E
     return chain_supported(dh);
 }
 
+bool aim_axis_folded(const ChainHost& ch, const float axis[3], float out[3])
+{
+    const double a[3] = {(double)axis[0], (double)axis[1], (double)axis[2]};
+    const double n = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+    if (!std::isfinite(n) || !(n >= 1e-6)) return false;  // (a NaN or infinite component makes n so)
+    for (int r = 0; r < 3; ++r)
+        out[r] = (float)(((double)ch.tip_rot[3 * r] * a[0] + (double)ch.tip_rot[3 * r + 1] * a[1] +
+                          (double)ch.tip_rot[3 * r + 2] * a[2]) /
+                         n);
+    return true;
+}
+
 }  // namespace ikpso

@@ -32,4 +32,9 @@ ikpso_status parse_chain(const std::vector<ikpso_node>& nodes, const ikpso_pso_c
 // when it does not fold.
 bool build_dh(const std::vector<ikpso_node>& nodes, const ChainHost& eu, const Extras& ex, ChainHost& dh);
 
+// ikpso_solve_track_aim's axis in the folded chain's frame: a' = G a / |a| (G = ch.tip_rot), formed in
+// fp64 and rounded once, so that R_eff a = W_J Rz(t_J) a'.  False, out untouched, for an axis that
+// is not finite or shorter than 1e-6.
+bool aim_axis_folded(const ChainHost& ch, const float axis[3], float out[3]);
+
 }  // namespace ikpso

@@ -597,7 +597,7 @@ __device__ __forceinline__ Frame child_frame(const Frame& P, float a, float b, f
 // and cooperative FAST builds with the hardware sin/cos (the streaming kernels
 // keep the reference's radian layout in HBM).
 constexpr int kTermPosRef = 1, kTermPenalty = 2, kTermRuntime = 4, kTermUniformBounds = 8, kTermColliders = 16,
-              kTermMask = 32, kTermRev = 64, kTermUnitBounds = 128, kTermSymPenalty = 256, kTermOrient = 512;
+              kTermMask = 32, kTermRev = 64, kTermUnitBounds = 128, kTermSymPenalty = 256, kTermOrient = 512, kTermAim = 1024;
 // kTermUnitBounds (with kTermRev and kTermUniformBounds): the clamp bounds are
 // exactly [0, 1] revolutions -- the reference scene's [0, 2pi] -- so the clamp
 // is the VALU's free output clamp on the position update instead of a v_med3
@@ -609,6 +609,8 @@ constexpr int kTermPosRef = 1, kTermPenalty = 2, kTermRuntime = 4, kTermUniformB
 // (half rate): BASELINE config 5's +-pi/2 soft limits inside +-pi.
 // kTermOrient (the folded chain's track kernels, ikpso_solve_track_pose): the tip orientation
 // term w |R_eff - R_target|_F^2, added last (TipBackAccDH).
+// kTermAim (the same kernels, ikpso_solve_track_aim; never with kTermOrient): the tool-axis term
+// w |R_eff a - d|^2 in its place.
 
 // Parity-attribution builds of FAST arithmetic (tools/tier_b_attribution.py; built into
 // variants/, never shipped): each switch removes one FAST ingredient --
@@ -1125,7 +1127,8 @@ struct TipBackAcc {
     const float* soft;
     float rot_diff, pen, ux, uy, uz;
 
-    __device__ __forceinline__ TipBackAcc(const float*, const float* soft_, const float* = nullptr)
+    __device__ __forceinline__ TipBackAcc(const float*, const float* soft_, const float* = nullptr,
+                                          const float* = nullptr)
         : soft(soft_), rot_diff(0.0f), pen(0.0f)
     {
     }
@@ -1203,15 +1206,22 @@ struct TipBackAccDH {
     const float* dhc;
     const float* soft;
     // kTermOrient: PoseTarget::v of the swarm's frame -- T' = R_target G^T (9, row-major), then the weight
+    // kTermAim: the frame's direction d (3), then the weight
     const float* pose;
+    // kTermAim: a' = G a of the kernel arguments (SwarmIO::aim_axis), scalar loads
+    const float* axis;
     float rot_diff, pen, ux, uy, uz;
     // kTermOrient: the x and y columns of the rotation C_k Rz(t_k) ... C_J Rz(t_J), carried from the tip
     // back beside u through the same constants (13 multiply-adds per column and joint; the z column is
     // their cross product, in finish).  After joint 1 they are columns of W_J Rz(t_J) = R_eff G^T.
     float ax, ay, az, bx, by, bz;
+    // kTermAim: the one vector C_k Rz(t_k) ... C_J Rz(t_J) a', carried the same way (13 multiply-adds
+    // per joint, no cross product).  After joint 1 it is W_J Rz(t_J) G a = R_eff a.
+    float vx, vy, vz;
 
-    __device__ __forceinline__ TipBackAccDH(const float* dh, const float* soft_, const float* pose_ = nullptr)
-        : dhc(dh), soft(soft_), pose(pose_), rot_diff(0.0f), pen(0.0f)
+    __device__ __forceinline__ TipBackAccDH(const float* dh, const float* soft_, const float* pose_ = nullptr,
+                                            const float* axis_ = nullptr)
+        : dhc(dh), soft(soft_), pose(pose_), axis(axis_), rot_diff(0.0f), pen(0.0f)
     {
     }
 
@@ -1257,6 +1267,13 @@ struct TipBackAccDH {
                 bz = C[6] * b0 + C[7] * b1 + C[8] * b2;
             }
         }
+        if constexpr (TERMS & kTermAim) {
+            const float q0 = k == J ? axis[0] : vx, q1 = k == J ? axis[1] : vy, q2 = k == J ? axis[2] : vz;
+            const float v0 = ct * q0 - st * q1, v1 = st * q0 + ct * q1;
+            vx = C[0] * v0 + C[1] * v1 + C[2] * q2;
+            vy = C[3] * v0 + C[4] * v1 + C[5] * q2;
+            vz = C[6] * v0 + C[7] * v1 + C[8] * q2;
+        }
     }
 
     __device__ __forceinline__ float finish(const ChainConsts<J>& cc, const float* tgt3) const
@@ -1277,6 +1294,11 @@ struct TipBackAccDH {
                                  ((d2 * d2 + d5 * d5) + d8 * d8);
             f = f + pose[9] * orient;
         }
+        if constexpr (TERMS & kTermAim) {
+            // |R_eff a - d|^2, d used as given; weight 0 adds an exact +0
+            const float gx = vx - pose[0], gy = vy - pose[1], gz = vz - pose[2];
+            f = f + pose[3] * ((gx * gx + gy * gy) + gz * gz);
+        }
         return f;
     }
 };
@@ -1290,16 +1312,18 @@ using TipAccFor =
 template <class Topo, int MODE, int TERMS>
 __device__ __forceinline__ float fitness(const ChainConsts<Topo::J>& cc, const float* x, const float* rest,
                                          const float* tgt, float* node_pos /* [3J] or nullptr */,
-                                         const float* dhc, const float* soft, const float* pose = nullptr)
+                                         const float* dhc, const float* soft, const float* pose = nullptr,
+                                         const float* axis = nullptr)
 {
-    static_assert(!(TERMS & kTermOrient) || (Topo::kDH && kTipBackward<Topo, MODE, TERMS>),
-                  "the orientation term: the folded chain's tip-backward builds");
+    static_assert(!(TERMS & (kTermOrient | kTermAim)) || (Topo::kDH && kTipBackward<Topo, MODE, TERMS>),
+                  "the orientation and aim terms: the folded chain's tip-backward builds");
+    static_assert((TERMS & (kTermOrient | kTermAim)) != (kTermOrient | kTermAim), "one tip term or the other");
     constexpr int A = Topo::A;
     if constexpr (kTipBackward<Topo, MODE, TERMS>) {
         if (!node_pos) {
             constexpr int J = Topo::J;
             using Acc = TipAccFor<Topo, MODE, TERMS>;
-            Acc tb(dhc, soft, pose);
+            Acc tb(dhc, soft, pose, axis);
 #pragma unroll
             for (int k = 1; k <= J; ++k) tb.angles(k, x + A * (k - 1), rest + A * (k - 1));
 #pragma unroll

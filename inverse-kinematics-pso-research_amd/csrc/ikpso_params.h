@@ -116,6 +116,13 @@ struct SwarmIO {
     float orient_w;
     const float* target_rot;
     float tip_rot[9];
+    // Aim track kernels only (ikpso_solve_track_aim; kTermAim): aim != 0 routes the launch to them.
+    // aim_dir: [frames][B][3] world directions, used as given; aim_axis: a' = G a, the caller's unit axis
+    // in the frame W_J Rz(t_J) (aim_axis_folded).  After the pose fields, for the same reason.
+    int32_t aim;
+    float aim_w;
+    const float* aim_dir;
+    float aim_axis[3];
 };
 
 // Streaming (state-in-HBM) kernels: one launch per PSO iteration over every

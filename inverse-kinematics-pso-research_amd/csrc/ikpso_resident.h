@@ -173,12 +173,13 @@ template <class Topo, int MODE, int TERMS, int BLOCK, int KA = 0, bool INV = fal
 __device__ __forceinline__ void swarm_step_tip(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh, float* s_pb,
                                                int tid, float (&x)[Topo::D], float (&v)[Topo::D], float& pbf,
                                                const PsoCoef& coef, Rng& rng, const float* pa = nullptr,
-                                               const float* pc = nullptr, const float* pose = nullptr)
+                                               const float* pc = nullptr, const float* pose = nullptr,
+                                               const float* axis = nullptr)
 {
     constexpr int J = Topo::J, A = Topo::A, D = Topo::D;
     constexpr int PL = D > kTrigAheadMaxD ? kPrioLevels2Wave : 0;  // wave priority: the 2-wave kernels
     using Acc = TipAccFor<Topo, MODE, TERMS>;
-    Acc acc(sh.dh, sh.soft, pose);  // pose: the kTermOrient builds' PoseTarget::v
+    Acc acc(sh.dh, sh.soft, pose, axis);  // pose: the kTermOrient / kTermAim builds' PoseTarget::v; axis: kTermAim
     float npb[A], ng[A], nrest[A];
 #pragma unroll
     for (int ax = 0; ax < A; ++ax) {
@@ -292,12 +293,13 @@ template <class Topo, int MODE, int TERMS, int BLOCK, int KV = 0, bool SPLIT = f
 __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh, float* s_pb,
                                            int tid, float (&x)[Topo::D], float (&v)[Topo::D], float& pbf,
                                            const PsoCoef& coef, Rng& rng, int tid_upper = 0,
-                                           const float* pose = nullptr)
+                                           const float* pose = nullptr, const float* axis = nullptr)
 {
     constexpr int J = Topo::J, A = Topo::A, D = Topo::D;
     constexpr bool MASK = kMasked<Topo, TERMS>;
     if constexpr (kTipBackward<Topo, MODE, TERMS>) {
-        swarm_step_tip<Topo, MODE, TERMS, BLOCK>(cc, sh, s_pb, tid, x, v, pbf, coef, rng, nullptr, nullptr, pose);
+        swarm_step_tip<Topo, MODE, TERMS, BLOCK>(cc, sh, s_pb, tid, x, v, pbf, coef, rng, nullptr, nullptr, pose,
+                                                 axis);
         return;
     }
     // (not the collider builds: the pipelined step's extra live node spilled them)
@@ -422,7 +424,8 @@ template <class Topo, int MODE, int TERMS, bool TUNED, class Rng>
 __device__ __forceinline__ void resident_iteration(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh, float* s_pb,
                                                    int tid, int tid_upper, int wave, bool active, const PsoCoef& coef,
                                                    int par, float (&x)[Topo::D], float (&v)[Topo::D], float& pbf,
-                                                   Rng& rng, uint32_t& gkey, int& bidx, const float* pose = nullptr)
+                                                   Rng& rng, uint32_t& gkey, int& bidx, const float* pose = nullptr,
+                                                   const float* axis = nullptr)
 {
     constexpr int BLOCK = kResidentMaxThreads<Topo::D>();
     constexpr int KV = kVelLds<Topo, MODE, TERMS>();
@@ -432,7 +435,8 @@ __device__ __forceinline__ void resident_iteration(const ChainConsts<Topo::J>& c
         const ChainConsts<Topo::J>& cci = kernarg_cc<Topo::J>();
         swarm_step<Topo, MODE, TERMS, BLOCK, KV>(cci, sh, s_pb, tid, x, v, pbf, pso_coef(cci), rng);
     } else {
-        swarm_step<Topo, MODE, TERMS, BLOCK, KV, TUNED>(cc, sh, s_pb, tid, x, v, pbf, coef, rng, tid_upper, pose);
+        swarm_step<Topo, MODE, TERMS, BLOCK, KV, TUNED>(cc, sh, s_pb, tid, x, v, pbf, coef, rng, tid_upper, pose,
+                                                        axis);
     }
 
     // thrust::min_element + `globalMin > currentGlobalMin` (src/kernel.cu:315-323)
@@ -591,10 +595,12 @@ __device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc,
 
     const PsoCoef coef = pso_coef(cc);
     float* const s_v = s_pb + D * BLOCK;  // (kVelLds)
+    const float* const axis = (TERMS & kTermAim) ? io.aim_axis : nullptr;  // a' (kernel argument)
     for (int32_t t = 0; t < io.frames; ++t) {
         const int64_t cell = (int64_t)t * io.num_swarms + b;  // (frame, swarm) in the time-major buffers
         stage_swarm_targets<Topo, TERMS>(cc, io.targets + cell * cc.num_eff * 3, sh);
         if constexpr (TERMS & kTermOrient) stage_swarm_orientation<Topo>(cc, io, cell, pose);
+        if constexpr (TERMS & kTermAim) stage_swarm_aim<Topo>(cc, io, cell, pose);
         __syncthreads();
 
         // initParticlesKernel, initLocalBests, first argmin and global-best copy (swarm_resident_body)
@@ -602,7 +608,7 @@ __device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc,
         init_particle<Topo, TERMS, BLOCK>(cc, sh, s_pb, tid, x, v, rng);
 #pragma unroll
         for (int d = 0; d < KV; ++d) s_v[d * BLOCK + tid] = v[d];
-        float pbf = fitness<Topo, MODE, TERMS>(cc, x, sh.rest, sh.tgt, nullptr, sh.dh, sh.soft, pose);
+        float pbf = fitness<Topo, MODE, TERMS>(cc, x, sh.rest, sh.tgt, nullptr, sh.dh, sh.soft, pose, axis);
         int bidx;
         uint32_t gkey = swarm_argmin(sh, 0, active ? ordered_key(pbf) : 0xFFFFFFFFu, &bidx);
         copy_gbest<Topo, BLOCK>(sh, s_pb, bidx);
@@ -612,7 +618,7 @@ __device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc,
         int it = 0;
         for (; it < io.iterations && gkey > io.stop_key; ++it)
             resident_iteration<Topo, MODE, TERMS, false>(cc, sh, s_pb, tid, 0, 0, active, coef, (it + 1) & 1, x, v, pbf,
-                                                         rng, gkey, bidx, pose);
+                                                         rng, gkey, bidx, pose, axis);
 
         // the frame's outputs
         compiler_fence();
@@ -670,9 +676,11 @@ __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWa
             swarm_track_body<Topo, MODE, TERMS>(cc, io, sh, s_pb);
         else
             swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, sh, s_pb);
-    } else if constexpr (TERMS & kTermOrient) {
-        // the pose track kernels (ikpso_solve_track_pose): the frame's orientation target beside the uniforms
-        static_assert(TRACK && Topo::kDH, "the orientation term: the folded chain's track kernels");
+    } else if constexpr (TERMS & (kTermOrient | kTermAim)) {
+        // the pose and aim track kernels (ikpso_solve_track_pose, ikpso_solve_track_aim): the frame's
+        // orientation target, or its direction, beside the uniforms
+        static_assert(TRACK && Topo::kDH, "the orientation and aim terms: the folded chain's track kernels");
+        static_assert((TERMS & (kTermOrient | kTermAim)) != (kTermOrient | kTermAim), "one tip term or the other");
         __shared__ SwarmLds<Topo, NPB, PoseTarget> lds;
         swarm_track_body<Topo, MODE, TERMS>(cc, io, lds.sh, lds.pb, lds.extra.v);
     } else {
@@ -806,6 +814,21 @@ inline hipError_t run_resident_pose(const ChainHost& ch, const SwarmIO& io, int 
     hipError_t err = hipErrorNotSupported;
     dh_terms<Topo>(term_set(ch), &err, [&](auto t) {
         return launch_resident_build<Topo, IKPSO_ARITH_FAST, decltype(t)::value | kTermRev | kTermOrient, true>(
+            cc, io, grid, threads, stream);
+    });
+    return err;
+}
+
+// The aim track kernels (ikpso_solve_track_aim): the same ladder with the tool-axis term.
+template <class Topo>
+inline hipError_t run_resident_aim(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
+{
+    static_assert(Topo::kDH, "the aim term: the folded chain");
+    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
+    const dim3 grid((unsigned)io.num_swarms), threads(block);
+    hipError_t err = hipErrorNotSupported;
+    dh_terms<Topo>(term_set(ch), &err, [&](auto t) {
+        return launch_resident_build<Topo, IKPSO_ARITH_FAST, decltype(t)::value | kTermRev | kTermAim, true>(
             cc, io, grid, threads, stream);
     });
     return err;

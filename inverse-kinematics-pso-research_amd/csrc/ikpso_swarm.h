@@ -101,7 +101,7 @@ __device__ __forceinline__ void stage_swarm_targets(const ChainConsts<Topo::J>& 
 
 // The pose track kernels' extra LDS (SwarmLds::Extra; kTermOrient): the orientation target of the
 // swarm's current frame, T' = R_target G^T row-major in v[0..8], and the term's weight
-// eff_w[tip] * orientation_weight in v[9].  No other build has it.
+// eff_w[tip] * orientation_weight in v[9].  Only they and the aim track kernels (below) have it.
 struct PoseTarget {
     float v[16];
 };
@@ -122,6 +122,19 @@ __device__ __forceinline__ void stage_swarm_orientation(const ChainConsts<Topo::
             pose[3 * i + c] = r0 * io.tip_rot[3 * c] + r1 * io.tip_rot[3 * c + 1] + r2 * io.tip_rot[3 * c + 2];
     }
     pose[9] = cc.eff_w[Topo::J] * io.orient_w;
+}
+
+// The aim track kernels (kTermAim) reuse the slot: the direction d of one (frame, swarm) cell, as
+// given, in v[0..2] and the term's weight eff_w[tip] * aim_weight in v[3].  A null aim_dir stages zeros.
+template <class Topo>
+__device__ __forceinline__ void stage_swarm_aim(const ChainConsts<Topo::J>& cc, const SwarmIO& io, int64_t cell,
+                                                float* pose)
+{
+    if (threadIdx.x != 0) return;
+    const float* d = io.aim_dir ? io.aim_dir + cell * 3 : nullptr;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pose[c] = d ? d[c] : 0.0f;
+    pose[3] = cc.eff_w[Topo::J] * io.aim_w;
 }
 
 // The uniforms that depend on the chain alone: folded-chain constants, soft limits and the

@@ -34,6 +34,12 @@ struct PoseOps {
     static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
+// The folded chain's aim track kernels (ikpso_solve_track_aim), likewise (ikpso_inst_aim_dh_*.hip).
+template <class Topo>
+struct AimOps {
+    static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -63,6 +69,13 @@ struct TopoOps {
             if (mode == IKPSO_ARITH_FAST) return PoseOps<Topo>::track(ch, io, block, s);
         }
         return hipErrorNotSupported;  // no other kernel has the orientation term
+    }
+    static hipError_t aim_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    {
+        if constexpr (Topo::kDH) {
+            if (mode == IKPSO_ARITH_FAST) return AimOps<Topo>::track(ch, io, block, s);
+        }
+        return hipErrorNotSupported;  // no other kernel has the aim term
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {

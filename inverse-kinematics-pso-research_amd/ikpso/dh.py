@@ -122,6 +122,12 @@ class DHArm:
         targets of solve_track / solve_until are measured in the effector node's frame."""
         return np.asarray(r_tool, dtype=np.float64) @ self.tool_rotation.T
 
+    def node_axis(self, tool_axis) -> np.ndarray:
+        """The effector-node-frame axis [3] that is tool_axis of the DH tool frame (R_tool a_tool =
+        R_node tool_rotation a_tool): the aim_axis of solve_track / solve_until for an axis named in
+        the textbook tool frame."""
+        return self.tool_rotation @ np.asarray(tool_axis, dtype=np.float64)
+
     @property
     def dof(self) -> int:
         """Scalar angles of the node table (3 per node, most locked)."""

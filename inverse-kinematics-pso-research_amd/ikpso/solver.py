@@ -296,9 +296,31 @@ class BatchSolver:
                                                     _dev_ptr(iters), _stream_handle(stream)),
                    "ikpso_solve_track_pose")
 
+    def _solve_aim(self, targets, aim_dir, aim_axis, aim_weight: float, start_pose, B: int, T: int, it: int,
+                   stop: float, outs, stream) -> None:
+        """ikpso_solve_track_aim over time-major buffers: aim_dir holds T * B world directions, aim_axis
+        (host, 3 values) the tool axis in the effector node's frame."""
+        torch = _torch()
+        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        if aim_dir.numel() != T * B * 3 or int(aim_dir.shape[-1]) != 3:
+            raise ValueError(f"aim_dir must hold {T * B} directions [..., 3]")
+        axis = np.asarray(aim_axis, dtype=np.float32).reshape(-1)
+        if axis.shape != (3,):
+            raise ValueError("aim_axis must hold 3 values")
+        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (aim_dir, "aim_dir")):
+            self._check_tensor(t, name, dev)
+        angles, fitness, res, iters = outs
+        host_axis = (ctypes.c_float * 3)(*axis.tolist())  # read during the call
+        _abi.check(self._lib.ikpso_solve_track_aim(self._h, _dev_ptr(targets), _dev_ptr(aim_dir), host_axis,
+                                                   float(aim_weight), _dev_ptr(start_pose), B, T, it, stop,
+                                                   _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
+                                                   _dev_ptr(iters), _stream_handle(stream)),
+                   "ikpso_solve_track_aim")
+
     def solve_until(self, targets=None, start_pose=None, max_iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, num_swarms: Optional[int] = None, residual: bool = True,
-                    stream=None, target_rot=None, orientation_weight: float = 0.0):
+                    stream=None, target_rot=None, orientation_weight: float = 0.0, aim_dir=None,
+                    aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0):
         """solve() with a per-swarm early stop (ikpso_solve_batch_until): swarm b stops after the
         first iteration n >= 0 at which its global-best fitness is <= stop_fitness, else it runs
         max_iterations (None: the solver's PSOConfig.iterations).  stop_fitness tests the fitness,
@@ -308,8 +330,11 @@ class BatchSolver:
         solve(iterations=n), bit for bit.  Runs the resident or the streaming kernels; a
         kernel="coop" solver raises (unsupported configuration).  Stream-ordered, asynchronous.
         target_rot (device [B, 3, 3] float32) with orientation_weight: the pose form, one frame of
-        solve_track's (see there); it needs targets."""
+        solve_track's (see there); it needs targets.  aim_dir (device [B, 3] float32) with aim_axis
+        and aim_weight: the aim form, likewise; not together with target_rot."""
         torch = _torch()
+        if target_rot is not None and aim_dir is not None:
+            raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
         if num_swarms is None:
             if targets is None:
                 raise ValueError("num_swarms is required when targets is None")
@@ -332,6 +357,12 @@ class BatchSolver:
             self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, 1, it, stop,
                              (angles, fitness, res, iters), stream)
             return angles, fitness, res, iters
+        if aim_dir is not None:
+            if targets is None:
+                raise ValueError("the aim form needs targets")
+            self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, 1, it, stop,
+                            (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
         _abi.check(self._lib.ikpso_solve_batch_until(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, it, stop,
@@ -342,7 +373,7 @@ class BatchSolver:
 
     def solve_track(self, targets, start_pose=None, iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, residual: bool = True, stream=None, target_rot=None,
-                    orientation_weight: float = 0.0):
+                    orientation_weight: float = 0.0, aim_dir=None, aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0):
         """B swarms following T waypoints each (ikpso_solve_track): targets is device [T, B, E, 3],
         time-major; frame t of swarm b is solve_until on targets[t] with `iterations` as its
         maximum (None: the solver's PSOConfig.iterations), warm-started from start_pose (device
@@ -360,8 +391,17 @@ class BatchSolver:
         the residual stays positional.  With weight 0 the answers equal the call without target_rot,
         bit for bit.  Only a FAST solver of a masked serial chain that folds, on the resident
         family, has the term; every other solver raises (unsupported configuration).  With
-        target_rot=None this is ikpso_solve_track as before."""
+        target_rot=None this is ikpso_solve_track as before.
+        aim_dir (device [T, B, 3] float32, world unit directions, used as given): aim targets
+        (ikpso_solve_track_aim), for tasks that fix a tool axis and leave the roll about it free.  Every
+        fitness then carries eff_w[tip] * aim_weight * |R_eff aim_axis - aim_dir|^2 instead, aim_axis
+        (3 host values, normalised by the library) in the effector NODE's frame (for an axis of a DH
+        arm's tool frame pass DHArm.node_axis(a_tool)).  The same solvers are served, weight 0 is
+        again the call without the term bit for bit, and passing both target_rot and aim_dir raises
+        ValueError."""
         torch = _torch()
+        if target_rot is not None and aim_dir is not None:
+            raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
         if targets is None or targets.dim() != 4:
             raise ValueError(f"targets must be [T, B, {self.effectors}, 3]")
         T, B = int(targets.shape[0]), int(targets.shape[1])
@@ -379,6 +419,10 @@ class BatchSolver:
         if target_rot is not None:
             self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, T, it, stop,
                              (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
+        if aim_dir is not None:
+            self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, T, it, stop,
+                            (angles, fitness, res, iters), stream)
             return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
