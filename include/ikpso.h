@@ -54,7 +54,7 @@ typedef struct ikpso_node {
     float length;
     float target_position[3]; /* effectors only */
     float target_rotation[3]; /* unused by the fitness (as in the reference); orientation targets are
-                                 an argument of ikpso_solve_track_pose */
+                                 an argument of ikpso_solve_track_pose and ikpso_solve_track_frames */
 } ikpso_node;
 
 /* XORWOW generator state with cuRAND's curandStateXORWOW layout (48 bytes),
@@ -372,6 +372,48 @@ ikpso_status ikpso_solve_track_aim(ikpso_solver* solver, const float* targets, c
                                    int64_t num_swarms, int32_t frames, int32_t max_iterations,
                                    float stop_fitness, float* out_angles, float* out_fitness,
                                    float* out_residual, int32_t* out_iterations, void* stream);
+
+/* Orientation targets per effector for Euler chains and trees: ikpso_solve_track with a
+ * rotation term for every effector (added after ABI 5; detect by symbol).  Every fitness
+ * of the call -- the local and global bests, the per-frame stop test, out_fitness -- is
+ * ikpso_solve_track's plus, accumulated over the effectors in node order and added last,
+ *   sum_e effector_weight[k_e] * rot_weights[e] * |R_{k_e} - target_rot[e]|_F^2
+ * where R_k is the world rotation of node k's frame as the Euler chain defines it (the
+ * origin's Rx Ry Rz, then Rx Ry Rz of every node down the path to k; links do not turn
+ * the frame: ikpso_solve_track_pose's definition) and k_e the node of effector e.
+ *   target_rot   device, [T][B][E][9]: row-major 3x3 rotations, time-major like targets,
+ *                effectors in node order exactly as targets indexes them; used as given.
+ *                May be NULL when every weight is 0.
+ *   rot_weights  HOST memory (as aim_axis is), E floats read during the call; the same
+ *                weights for every swarm and frame.  Each finite and >= 0; a weight of 0
+ *                leaves that effector position-only (fingertips).  NULL: all weights 0.
+ * With all weights 0 (or NULL) the call runs the kernel ikpso_solve_track runs and equals
+ * it bit for bit in outputs, iteration counts and generator states (the kernels with the
+ * term evaluate the position term by the same expressions in the runtime-term build's
+ * form, whose rounding may differ from a specialised build's, as between any two FAST
+ * builds).
+ * Everything else is ikpso_solve_track's contract: a fresh swarm per frame warm-started
+ * from the previous answer; the per-frame stop on the whole fitness, this term included;
+ * frames == 1 the form of solve_batch_until, a negative stop_fitness never stops; a
+ * particle draws D + 3 D n values; out_residual stays the positional checkDistance
+ * residual.  ikpso_solver_evaluate is unchanged: its fitness never includes this term.
+ * IKPSO_ERR_INVALID_ARG: a NaN stop_fitness; a NaN, infinite or negative weight; some
+ * weight > 0 with a NULL target_rot; frames > 0 with a NULL targets or out_angles.
+ * IKPSO_ERR_UNSUPPORTED (before the frames == 0 / num_swarms == 0 return, which is
+ * IKPSO_OK with no device work): served is a FAST solver of an unmasked Euler chain or
+ * tree with no collider term that its kernels test -- any compiled topology: the
+ * reference tree, the serial-tip widths, generic trees of 1..20 joints; the distance
+ * term and the soft-limit penalty are allowed -- created on the resident family with a
+ * swarm that fits one workgroup.  Refused: REFERENCE arithmetic; any axis mask, whether
+ * it folds or not, IKPSO_FLAG_NO_FOLD included (folded arms have
+ * ikpso_solve_track_pose); a chain whose collider term is live; a streaming or
+ * cooperative solver, requested or picked by AUTO.  No kernel without the term is ever
+ * run in the place of one with it. */
+ikpso_status ikpso_solve_track_frames(ikpso_solver* solver, const float* targets, const float* target_rot,
+                                      const float* rot_weights, const float* start_pose, int64_t num_swarms,
+                                      int32_t frames, int32_t max_iterations, float stop_fitness,
+                                      float* out_angles, float* out_fitness, float* out_residual,
+                                      int32_t* out_iterations, void* stream);
 
 /* Settle the last solve_batch (ABI >= 3).  After a cooperative-family solve:
  * wait for it and, if a group gave up (the GPU shared with other work), restore

@@ -2,6 +2,7 @@
 // dispatch to the gfx950 kernels.  The chain parser is ikpso_chain.cpp.
 #include <hip/hip_runtime.h>
 
+#include <float.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -438,6 +439,11 @@ struct SolveArgs {
     const float* aim_dir = nullptr;
     float aim_weight = 0.0f;
     float aim_axis[3] = {0.0f, 0.0f, 0.0f};
+    // ikpso_solve_track_frames: the effector-frame track kernels, with the rotations [frames][B][E][9] and
+    // the caller's weight per effector
+    bool eff_frames = false;
+    const float* eff_rot = nullptr;
+    float eff_rot_w[kMaxEffFrames] = {};
 };
 
 // The kernels the last solve ran, for ikpso_solver_kernel_name.
@@ -448,6 +454,7 @@ enum Route {
     // A resident AUTO solver of a long chain (256-lane chunks: no separate latency build) still
     // takes the cooperative route for a swarm of one chunk: the name reported is that kernel's.
     kRouteCoop,
+    kRouteFrames,  // the resident track kernels with the effector rotation term (ikpso_solve_track_frames)
     kRouteCount
 };
 
@@ -532,6 +539,9 @@ SwarmIO swarm_io(const ikpso_solver* s, const SolveArgs& a)
     io.aim_w = a.aim_weight;
     io.aim_dir = a.aim_dir;
     for (int i = 0; i < 3; ++i) io.aim_axis[i] = a.aim_axis[i];
+    io.eff_frames = a.eff_frames ? 1 : 0;
+    io.eff_rot = a.eff_rot;
+    for (int i = 0; i < kMaxEffFrames; ++i) io.eff_rot_w[i] = a.eff_rot_w[i];
     return io;
 }
 
@@ -823,6 +833,7 @@ ikpso_status ikpso_solver_create(const ikpso_solver_desc* desc, ikpso_solver** o
     s->kname[kRouteOwn] = kernel_name(sch, s->family);
     s->kname[kRouteStream] = kernel_name(sch, IKPSO_KERNEL_STREAMING);
     s->kname[kRouteCoop] = kernel_name(sch, IKPSO_KERNEL_COOP);
+    s->kname[kRouteFrames] = kernel_name(sch, IKPSO_KERNEL_RESIDENT).insert(strlen("swarm_resident"), "_frames");
     s->kname[kRouteLatency] = s->kname[kRouteCoop] +
                               (coop_latency_split(sch) ? " (latency variant, generator waves)" : " (latency variant)");
     *out = s;
@@ -976,6 +987,45 @@ ikpso_status ikpso_solve_track_aim(ikpso_solver* s, const float* targets, const 
     if (st != IKPSO_OK) return st;
     a.aim_dir = aim_dir;
     a.aim_weight = aim_weight;
+    return solve_resident(s, a, (hipStream_t)stream);
+}
+
+// ikpso_solve_track on the Euler topologies' effector-frame kernels: the same frame loop in one launch,
+// a rotation term per effector in every fitness.  Only the FAST runtime-term track build without mask or
+// collider block has the term, so only the solvers that build can serve are served.
+ikpso_status ikpso_solve_track_frames(ikpso_solver* s, const float* targets, const float* target_rot,
+                                      const float* rot_weights, const float* start_pose, int64_t num_swarms,
+                                      int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
+                                      float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
+{
+    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
+        return IKPSO_ERR_INVALID_ARG;
+    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
+    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
+                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
+    const int E = s->chain.E;
+    for (int e = 0; rot_weights && e < E; ++e) {
+        const float w = rot_weights[e];
+        if (!(w >= 0.0f) || w > FLT_MAX) return IKPSO_ERR_INVALID_ARG;  // NaN, negative or infinite
+        if (e < kMaxEffFrames) a.eff_rot_w[e] = w;
+        a.eff_frames = a.eff_frames || w > 0.0f;
+    }
+    if (a.eff_frames && !target_rot) return IKPSO_ERR_INVALID_ARG;
+    // the refusal ladder: REFERENCE arithmetic; any axis mask (folded, or kept by IKPSO_FLAG_NO_FOLD); a
+    // collider term the kernels test (or their polynomial sin/cos); another family than the resident one
+    const ChainHost& ch = s->chain;
+    if (s->mode != IKPSO_ARITH_FAST || s->use_dh || ch.masked || ch.num_coll > 0 || ch.poly_trig ||
+        s->family != IKPSO_KERNEL_RESIDENT || E > kMaxEffFrames)
+        return IKPSO_ERR_UNSUPPORTED;
+    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
+    const ikpso_status st = begin_solve(s, num_swarms, true);
+    if (st != IKPSO_OK) return st;
+    // Every weight 0 is the term absent: the plain track kernel computes that fitness, and only it gives
+    // ikpso_solve_track's bits (as in ikpso_solve_track_pose).
+    if (a.eff_frames) {
+        a.eff_rot = target_rot;
+        s->last = kRouteFrames;
+    }
     return solve_resident(s, a, (hipStream_t)stream);
 }
 

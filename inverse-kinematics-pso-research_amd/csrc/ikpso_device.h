@@ -611,6 +611,11 @@ constexpr int kTermPosRef = 1, kTermPenalty = 2, kTermRuntime = 4, kTermUniformB
 // term w |R_eff - R_target|_F^2, added last (TipBackAccDH).
 // kTermAim (the same kernels, ikpso_solve_track_aim; never with kTermOrient): the tool-axis term
 // w |R_eff a - d|^2 in its place.
+// kTermOrient on an Euler topology (with kTermRuntime, FAST; ikpso_solve_track_frames): a rotation term
+// per effector, sum_e w_e |R_e - R_target,e|_F^2 over the node frames the forward accumulator composes
+// anyway (FitnessAcc), added last.  The targets and weights are staged per node, kEffFrame floats each
+// (EffFrames, ikpso_swarm.h): the rotation row-major, then the weight.
+constexpr int kEffFrame = 10;
 
 // Parity-attribution builds of FAST arithmetic (tools/tier_b_attribution.py; built into
 // variants/, never shipped): each switch removes one FAST ingredient --
@@ -747,6 +752,14 @@ struct FitnessAcc {
     float* cand;
     bool hit;
     const float* nearc = nullptr;  // the swarm kernels' SwarmShared::near4 (near_collider_lds), else null
+    // kTermOrient (ikpso_solve_track_frames): the staged rotation targets and weights per node (EffFrames::v,
+    // LDS; set by the caller after construction) and the term's sum over the effectors, in node order
+    static_assert(!(TERMS & kTermOrient) ||
+                      (MODE == IKPSO_ARITH_FAST && (TERMS & kTermRuntime) &&
+                       !(TERMS & (kTermColliders | kTermMask | kTermRev | kTermAim))),
+                  "the effector rotation term: the FAST runtime-term builds without colliders or mask");
+    const float* rot = nullptr;
+    float orient = 0.0f;
 
     // soft_: the soft limits -- pass the swarm kernel's LDS copy (SwarmShared::soft)
     // where there is one: a pointer that may be LDS or global is a flat pointer
@@ -761,7 +774,10 @@ struct FitnessAcc {
 
     // Node k (1..J) with its three Euler angles, its three rest angles and (for
     // effectors) its target; nodes must come in index order.
-    // column-wise composition unless only the leaf's position is consumed
+    // column-wise composition unless only the leaf's position is consumed.  The effector rotation term
+    // (kTermOrient) consumes a leaf's whole rotation too, and both forms give it; its leaves keep the
+    // closed form all the same: composed column-wise the reference tree's build spilled 83 registers
+    // (60 scratch accesses per iteration) against 20 (18 per iteration) in the closed form.
     __device__ __forceinline__ static constexpr bool seq(int k)
     {
         return !Topo::kGeneric && (!Topo::leaf(k) || (TERMS & kTermColliders));
@@ -846,6 +862,22 @@ struct FitnessAcc {
             } else {
 #pragma clang fp contract(fast)
                 distance = distance + ((ex * ex + ey * ey) + ez * ez) * cc.eff_w[k];
+            }
+            if constexpr (TERMS & kTermOrient) {
+                // The effector's rotation term: nine squared differences of F[k]'s rotation against the
+                // staged target, times the staged weight.  The weight is the same in every lane (one LDS
+                // word): an effector of weight 0 -- and a generic tree's node that is no effector -- is
+                // skipped by a uniform branch.
+                const float* q = rot + kEffFrame * (k - 1);
+                const float w = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(q[9])));
+                if (w != 0.0f) {
+#pragma clang fp contract(fast)
+                    const float d0 = F[k].r00 - q[0], d1 = F[k].r01 - q[1], d2 = F[k].r02 - q[2];
+                    const float d3 = F[k].r10 - q[3], d4 = F[k].r11 - q[4], d5 = F[k].r12 - q[5];
+                    const float d6 = F[k].r20 - q[6], d7 = F[k].r21 - q[7], d8 = F[k].r22 - q[8];
+                    orient = orient + w * ((((d0 * d0 + d1 * d1) + d2 * d2) + ((d3 * d3 + d4 * d4) + d5 * d5)) +
+                                           ((d6 * d6 + d7 * d7) + d8 * d8));
+                }
             }
         }
         if (penalty) {  // soft joint-limit penalty (extension, BASELINE config 5), d order
@@ -932,6 +964,7 @@ struct FitnessAcc {
         const float aw = angle_weight<TERMS>(cc);
         float f = posref ? (distance + cc.dw_j * pos_diff) + aw * rot_diff : distance + aw * rot_diff;
         if (penalty) f = f + limit_weight<TERMS>(cc) * pen;
+        if constexpr (TERMS & kTermOrient) f = f + orient;  // (ikpso_solve_track_frames: added last)
         if constexpr (TERMS & kTermColliders) {
             if (hit) f = FLT_MAX;  // (generic trees)
             uint32_t m = (f >= pbest && pbest <= FLT_MAX) ? 0u : near_mask;
@@ -1315,8 +1348,13 @@ __device__ __forceinline__ float fitness(const ChainConsts<Topo::J>& cc, const f
                                          const float* dhc, const float* soft, const float* pose = nullptr,
                                          const float* axis = nullptr)
 {
-    static_assert(!(TERMS & (kTermOrient | kTermAim)) || (Topo::kDH && kTipBackward<Topo, MODE, TERMS>),
-                  "the orientation and aim terms: the folded chain's tip-backward builds");
+    // the folded chain keeps the tip-backward form of both terms; an Euler topology has the orientation
+    // term alone, per effector, in the forward form of its runtime-term build (FitnessAcc)
+    static_assert(!(TERMS & (kTermOrient | kTermAim)) ||
+                      (Topo::kDH ? kTipBackward<Topo, MODE, TERMS>
+                                 : (MODE == IKPSO_ARITH_FAST && (TERMS & kTermRuntime) && !(TERMS & kTermAim))),
+                  "the orientation and aim terms: the folded chain's tip-backward builds; the orientation term "
+                  "also the Euler topologies' FAST runtime-term builds");
     static_assert((TERMS & (kTermOrient | kTermAim)) != (kTermOrient | kTermAim), "one tip term or the other");
     constexpr int A = Topo::A;
     if constexpr (kTipBackward<Topo, MODE, TERMS>) {
@@ -1333,6 +1371,7 @@ __device__ __forceinline__ float fitness(const ChainConsts<Topo::J>& cc, const f
     }
     CandBuf<Topo, TERMS> cb;
     FitnessFor<Topo, MODE, TERMS> acc(cc, dhc, soft, cb.v);
+    if constexpr (!Topo::kDH && (TERMS & kTermOrient)) acc.rot = pose;  // (EffFrames::v)
 #pragma unroll
     for (int k = 1; k <= Topo::J; ++k) {
         acc.node(cc, k, x + A * (k - 1), rest + A * (k - 1), tgt + 3 * (k - 1), node_pos);

@@ -102,6 +102,7 @@ hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hip
         using T = decltype(topo);
         if (io.pose) return TopoOps<T>::pose_track(ch, mode, io, block, stream);  // (ikpso_solve_track_pose)
         if (io.aim) return TopoOps<T>::aim_track(ch, mode, io, block, stream);    // (ikpso_solve_track_aim)
+        if (io.eff_frames) return TopoOps<T>::frames_track(ch, mode, io, block, stream);  // (ikpso_solve_track_frames)
         return io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
                              : TopoOps<T>::resident(ch, mode, io, block, stream);
     });

@@ -8,6 +8,8 @@
 namespace ikpso {
 
 constexpr int kMaxJoints = 32;
+// Effectors ikpso_solve_track_frames carries weights for: every node of the widest compiled tree.
+constexpr int kMaxEffFrames = 20;
 
 // Per-chain constants, passed by value so they land in the kernarg segment and
 // are read with scalar loads (the chain is identical for every particle and
@@ -123,6 +125,13 @@ struct SwarmIO {
     float aim_w;
     const float* aim_dir;
     float aim_axis[3];
+    // Effector-frame track kernels only (ikpso_solve_track_frames; kTermOrient on the Euler topologies):
+    // eff_frames != 0 routes the launch to them.  eff_rot: [frames][B][E][9] row-major rotations per
+    // effector, in node order as targets; eff_rot_w: the caller's weight per effector slot (0: the
+    // effector stays position-only).  After the aim fields, for the same reason.
+    int32_t eff_frames;
+    const float* eff_rot;
+    float eff_rot_w[kMaxEffFrames];
 };
 
 // Streaming (state-in-HBM) kernels: one launch per PSO iteration over every

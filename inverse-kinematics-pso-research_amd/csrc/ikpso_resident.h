@@ -134,12 +134,14 @@ __device__ __forceinline__ void update_node(const ChainConsts<Topo::J>& cc, cons
 template <class Topo, int MODE, int TERMS, int BLOCK, bool SPLIT = false, class Rng>
 __device__ __forceinline__ float swarm_step_ahead(const ChainConsts<Topo::J>& cc, SwarmShared<Topo>& sh,
                                                   float* s_pb, const PbLane<BLOCK, SPLIT>& pbl, float (&x)[Topo::D],
-                                                  float (&v)[Topo::D], const PsoCoef& coef, Rng& rng)
+                                                  float (&v)[Topo::D], const PsoCoef& coef, Rng& rng,
+                                                  const float* pose = nullptr)
 {
     constexpr int J = Topo::J, A = Topo::A;
     constexpr int HW = kHwTrig<Topo, MODE, TERMS>;
     CandBuf<Topo, TERMS> cb;
     FitnessFor<Topo, MODE, TERMS> acc(cc, sh.dh, sh.soft, cb.v);
+    if constexpr (!Topo::kDH && (TERMS & kTermOrient)) acc.rot = pose;  // (ikpso_solve_track_frames: EffFrames::v)
     progress_prio<J, kPrioLevels4Wave>(1);
     update_node<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, 1, x, v, coef, rng);
     NodeTrig<A> cur = node_trig<HW, A>(x);
@@ -306,7 +308,7 @@ __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, Swarm
     if constexpr (MODE == IKPSO_ARITH_FAST && Topo::D <= kTrigAheadMaxD && !(TERMS & kTermColliders)) {
         // updateLocalBests (src/kernel.cu:202-221): strict improvement
         const PbLane<BLOCK, SPLIT> pbl{tid, tid_upper};
-        const float f = swarm_step_ahead<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, x, v, coef, rng);
+        const float f = swarm_step_ahead<Topo, MODE, TERMS, BLOCK, SPLIT>(cc, sh, s_pb, pbl, x, v, coef, rng, pose);
         if (f < pbf) {
             pbf = f;
 #pragma unroll
@@ -318,6 +320,7 @@ __device__ __forceinline__ void swarm_step(const ChainConsts<Topo::J>& cc, Swarm
     FitnessFor<Topo, MODE, TERMS> acc(cc, sh.dh, sh.soft, cb.v);
     if constexpr ((TERMS & kTermColliders) && SwarmShared<Topo>::kNear > 0 && !IKPSO_COLLIDE_STATS)
         acc.nearc = sh.near4;  // (the counting builds count through near_collider)
+    if constexpr (!Topo::kDH && (TERMS & kTermOrient)) acc.rot = pose;  // (ikpso_solve_track_frames: EffFrames::v)
     float* const s_v = s_pb + D * BLOCK;  // KV > 0: velocities [d][lane] (kVelLds)
     // node kk's local bests, global best, rest angles, target and LDS velocities
     auto load_node = [&](int kk, float (&pb)[A], float (&g)[A], float (&rest)[A], float (&tgt)[3], float (&vv)[A]) {
@@ -599,7 +602,12 @@ __device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc,
     for (int32_t t = 0; t < io.frames; ++t) {
         const int64_t cell = (int64_t)t * io.num_swarms + b;  // (frame, swarm) in the time-major buffers
         stage_swarm_targets<Topo, TERMS>(cc, io.targets + cell * cc.num_eff * 3, sh);
-        if constexpr (TERMS & kTermOrient) stage_swarm_orientation<Topo>(cc, io, cell, pose);
+        if constexpr (TERMS & kTermOrient) {
+            if constexpr (Topo::kDH)
+                stage_swarm_orientation<Topo>(cc, io, cell, pose);
+            else
+                stage_swarm_frames<Topo>(cc, io, cell, pose);  // (ikpso_solve_track_frames)
+        }
         if constexpr (TERMS & kTermAim) stage_swarm_aim<Topo>(cc, io, cell, pose);
         __syncthreads();
 
@@ -657,6 +665,9 @@ __device__ __forceinline__ void swarm_track_body(const ChainConsts<Topo::J>& cc,
 // 1024-lane workgroup per CU, 4 waves per SIMD.
 template <class Topo>
 constexpr int kResidentMinWaves = Topo::kDH ? 8 : 1;
+// The LDS one resident workgroup may hold: a CU's 160 KiB (kResidentMaxThreads is sized so that the
+// uniforms and D local bests per lane fit it).
+constexpr size_t kResidentLdsBytes = 160 * 1024;
 
 // TRACK (ikpso_solve_track): the stopping kernel's twin with the frame loop (swarm_track_body),
 // instantiated in units of its own (TrackOps, ikpso_inst_track_*.hip).
@@ -672,10 +683,23 @@ __global__ void __launch_bounds__(kResidentMaxThreads<Topo::D>(), kResidentMinWa
         // LDS object (an illegal flat-to-LDS check)
         __shared__ SwarmShared<Topo> sh;
         __shared__ float s_pb[NPB];
-        if constexpr (TRACK)
+        if constexpr (TERMS & kTermOrient) {
+            // the effector-frame track kernels (ikpso_solve_track_frames): the frame's rotation targets in
+            // an object of their own again
+            static_assert(TRACK && (TERMS & kTermRuntime), "the effector rotation term: the runtime-term track kernels");
+            __shared__ EffFrames<Topo::J> rot;
+            static_assert(sizeof(sh) + sizeof(s_pb) + sizeof(rot) <= kResidentLdsBytes, "the workgroup's LDS");
+            swarm_track_body<Topo, MODE, TERMS>(cc, io, sh, s_pb, rot.v);
+        } else if constexpr (TRACK)
             swarm_track_body<Topo, MODE, TERMS>(cc, io, sh, s_pb);
         else
             swarm_resident_body<Topo, MODE, TERMS, STOP>(cc, io, sh, s_pb);
+    } else if constexpr ((TERMS & kTermOrient) && !Topo::kDH) {
+        // the same kernels of the compiled Euler topologies: the targets beside the uniforms
+        static_assert(TRACK && (TERMS & kTermRuntime), "the effector rotation term: the runtime-term track kernels");
+        __shared__ SwarmLds<Topo, NPB, EffFrames<Topo::J>> lds;
+        static_assert(sizeof(lds) <= kResidentLdsBytes, "the workgroup's LDS");
+        swarm_track_body<Topo, MODE, TERMS>(cc, io, lds.sh, lds.pb, lds.extra.v);
     } else if constexpr (TERMS & (kTermOrient | kTermAim)) {
         // the pose and aim track kernels (ikpso_solve_track_pose, ikpso_solve_track_aim): the frame's
         // orientation target, or its direction, beside the uniforms
@@ -817,6 +841,20 @@ inline hipError_t run_resident_pose(const ChainHost& ch, const SwarmIO& io, int 
             cc, io, grid, threads, stream);
     });
     return err;
+}
+
+// The effector-frame track kernels (ikpso_solve_track_frames): the runtime-term track build of an Euler
+// topology with the rotation term per effector, FAST.  A masked chain, a collider term (or the
+// polynomial sin/cos its builds carry) has no such build: the host refuses those solvers.
+template <class Topo>
+inline hipError_t run_resident_frames(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
+{
+    static_assert(!Topo::kDH, "the effector rotation term: the Euler topologies");
+    if (ch.masked || ch.num_coll > 0 || ch.poly_trig) return hipErrorNotSupported;
+    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
+    const dim3 grid((unsigned)io.num_swarms), threads(block);
+    return launch_resident_build<Topo, IKPSO_ARITH_FAST, kTermRuntime | kTermOrient, true>(cc, io, grid, threads,
+                                                                                          stream);
 }
 
 // The aim track kernels (ikpso_solve_track_aim): the same ladder with the tool-axis term.

@@ -137,6 +137,38 @@ __device__ __forceinline__ void stage_swarm_aim(const ChainConsts<Topo::J>& cc, 
     pose[3] = cc.eff_w[Topo::J] * io.aim_w;
 }
 
+// The effector-frame track kernels' extra LDS (ikpso_solve_track_frames; kTermOrient on the Euler
+// topologies), laid out per node like SwarmShared::tgt: at kEffFrame (k - 1) the target rotation of
+// node k in the swarm's current frame (9, row-major) and the term's weight eff_w[k] * rot_weights[slot];
+// a node that is no effector, or whose caller's weight is 0, has weight 0 and zeros for its rotation.
+template <int J>
+struct EffFrames {
+    float v[kEffFrame * J];
+};
+
+// One (frame, swarm) cell's rotations and weights, node k + 1 by thread k; the caller barriers.  The
+// caller's weights sit in the kernel arguments and are picked by constant indices (a select per slot:
+// a run-time index into the by-value block would cost a private copy of it).  A weight of 0 reads no
+// rotation, so eff_rot may be null when every weight is.
+template <class Topo>
+__device__ __forceinline__ void stage_swarm_frames(const ChainConsts<Topo::J>& cc, const SwarmIO& io, int64_t cell,
+                                                   float* rot)
+{
+    constexpr int J = Topo::J;
+    static_assert(J <= kMaxEffFrames, "a weight slot for every node");
+    for (int k = threadIdx.x; k < J; k += blockDim.x) {
+        const int s = cc.eff_slot[k + 1];
+        float rw = 0.0f;
+#pragma unroll
+        for (int e = 0; e < kMaxEffFrames; ++e) rw = s == e ? io.eff_rot_w[e] : rw;
+        const float w = cc.eff_w[k + 1] * rw;
+        const float* r = (w != 0.0f && io.eff_rot) ? io.eff_rot + (cell * cc.num_eff + s) * 9 : nullptr;
+#pragma unroll
+        for (int i = 0; i < 9; ++i) rot[kEffFrame * k + i] = r ? r[i] : 0.0f;
+        rot[kEffFrame * k + 9] = r ? w : 0.0f;
+    }
+}
+
 // The uniforms that depend on the chain alone: folded-chain constants, soft limits and the
 // near-collider table.
 template <class Topo, int TERMS = 0>

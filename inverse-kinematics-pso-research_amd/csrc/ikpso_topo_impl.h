@@ -1,5 +1,5 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, PoseOps<Topo> and AimOps<Topo>;
-// include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, PoseOps<Topo>, AimOps<Topo> and
+// FramesOps<Topo>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
@@ -31,6 +31,12 @@ template <class Topo>
 hipError_t AimOps<Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
 {
     return run_resident_aim<Topo>(ch, io, block, s);
+}
+
+template <class Topo>
+hipError_t FramesOps<Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
+{
+    return run_resident_frames<Topo>(ch, io, block, s);
 }
 
 template <class Topo, int MODE>

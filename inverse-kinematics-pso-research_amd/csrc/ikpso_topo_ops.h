@@ -40,6 +40,13 @@ struct AimOps {
     static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
+// The Euler topologies' effector-frame track kernels (ikpso_solve_track_frames; FAST, every topology but
+// TopoDH), likewise (ikpso_inst_frames_*.hip).
+template <class Topo>
+struct FramesOps {
+    static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -76,6 +83,13 @@ struct TopoOps {
             if (mode == IKPSO_ARITH_FAST) return AimOps<Topo>::track(ch, io, block, s);
         }
         return hipErrorNotSupported;  // no other kernel has the aim term
+    }
+    static hipError_t frames_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    {
+        if constexpr (!Topo::kDH) {
+            if (mode == IKPSO_ARITH_FAST) return FramesOps<Topo>::track(ch, io, block, s);
+        }
+        return hipErrorNotSupported;  // no other kernel has the effector rotation term
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {

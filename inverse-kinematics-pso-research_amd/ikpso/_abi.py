@@ -141,6 +141,7 @@ SIGNATURES = {
     "ikpso_solve_track": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
     "ikpso_solve_track_pose": (_i32, [_vp, _vp, _vp, _f, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
     "ikpso_solve_track_aim": (_i32, [_vp, _vp, _vp, _vp, _f, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
+    "ikpso_solve_track_frames": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f, _vp, _vp, _vp, _vp, _vp]),
     "ikpso_solver_sync": (_i32, [_vp]),
     "ikpso_solver_fallbacks": (_i64, [_vp]),
     "ikpso_coop_fallbacks": (_i64, []),

@@ -317,10 +317,37 @@ class BatchSolver:
                                                    _dev_ptr(iters), _stream_handle(stream)),
                    "ikpso_solve_track_aim")
 
+    def _solve_frames(self, targets, effector_rot, effector_rot_weight, start_pose, B: int, T: int, it: int,
+                      stop: float, outs, stream) -> None:
+        """ikpso_solve_track_frames over time-major buffers: effector_rot holds T * B * E row-major 3x3
+        rotations (or is None with every weight 0), effector_rot_weight one weight or E of them (host)."""
+        torch = _torch()
+        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        E = self.effectors
+        if effector_rot is not None and (effector_rot.numel() != T * B * E * 9 or
+                                         tuple(effector_rot.shape[-2:]) != (3, 3)):
+            raise ValueError(f"effector_rot must hold {T * B * E} rotations [..., {E}, 3, 3]")
+        host_w = None  # no weights: every weight 0
+        if effector_rot_weight is not None:
+            w = np.asarray(effector_rot_weight, dtype=np.float32).reshape(-1)
+            if w.size == 1:
+                w = np.repeat(w, E)
+            if w.shape != (E,):
+                raise ValueError(f"effector_rot_weight must be a scalar or hold {E} values")
+            host_w = (ctypes.c_float * E)(*w.tolist())  # read during the call
+        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (effector_rot, "effector_rot")):
+            self._check_tensor(t, name, dev)
+        angles, fitness, res, iters = outs
+        _abi.check(self._lib.ikpso_solve_track_frames(self._h, _dev_ptr(targets), _dev_ptr(effector_rot), host_w,
+                                                      _dev_ptr(start_pose), B, T, it, stop, _dev_ptr(angles),
+                                                      _dev_ptr(fitness), _dev_ptr(res), _dev_ptr(iters),
+                                                      _stream_handle(stream)),
+                   "ikpso_solve_track_frames")
+
     def solve_until(self, targets=None, start_pose=None, max_iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, num_swarms: Optional[int] = None, residual: bool = True,
                     stream=None, target_rot=None, orientation_weight: float = 0.0, aim_dir=None,
-                    aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0):
+                    aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0, effector_rot=None, effector_rot_weight=None):
         """solve() with a per-swarm early stop (ikpso_solve_batch_until): swarm b stops after the
         first iteration n >= 0 at which its global-best fitness is <= stop_fitness, else it runs
         max_iterations (None: the solver's PSOConfig.iterations).  stop_fitness tests the fitness,
@@ -331,10 +358,15 @@ class BatchSolver:
         kernel="coop" solver raises (unsupported configuration).  Stream-ordered, asynchronous.
         target_rot (device [B, 3, 3] float32) with orientation_weight: the pose form, one frame of
         solve_track's (see there); it needs targets.  aim_dir (device [B, 3] float32) with aim_axis
-        and aim_weight: the aim form, likewise; not together with target_rot."""
+        and aim_weight: the aim form, likewise; not together with target_rot.  effector_rot (device
+        [B, E, 3, 3] float32) with effector_rot_weight: per-effector orientation targets of an unmasked
+        Euler chain or tree, one frame of solve_track's; not together with either."""
         torch = _torch()
         if target_rot is not None and aim_dir is not None:
             raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
+        frames_form = effector_rot is not None or effector_rot_weight is not None
+        if frames_form and (target_rot is not None or aim_dir is not None):
+            raise ValueError("effector_rot is not combined with target_rot or aim_dir: pass one or the other")
         if num_swarms is None:
             if targets is None:
                 raise ValueError("num_swarms is required when targets is None")
@@ -363,6 +395,12 @@ class BatchSolver:
             self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, 1, it, stop,
                             (angles, fitness, res, iters), stream)
             return angles, fitness, res, iters
+        if frames_form:
+            if targets is None:
+                raise ValueError("the effector_rot form needs targets")
+            self._solve_frames(targets, effector_rot, effector_rot_weight,
+                               start_pose, B, 1, it, stop, (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
         _abi.check(self._lib.ikpso_solve_batch_until(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, it, stop,
@@ -373,7 +411,8 @@ class BatchSolver:
 
     def solve_track(self, targets, start_pose=None, iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, residual: bool = True, stream=None, target_rot=None,
-                    orientation_weight: float = 0.0, aim_dir=None, aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0):
+                    orientation_weight: float = 0.0, aim_dir=None, aim_axis=(0.0, 0.0, 1.0), aim_weight: float = 0.0,
+                    effector_rot=None, effector_rot_weight=None):
         """B swarms following T waypoints each (ikpso_solve_track): targets is device [T, B, E, 3],
         time-major; frame t of swarm b is solve_until on targets[t] with `iterations` as its
         maximum (None: the solver's PSOConfig.iterations), warm-started from start_pose (device
@@ -398,10 +437,22 @@ class BatchSolver:
         (3 host values, normalised by the library) in the effector NODE's frame (for an axis of a DH
         arm's tool frame pass DHArm.node_axis(a_tool)).  The same solvers are served, weight 0 is
         again the call without the term bit for bit, and passing both target_rot and aim_dir raises
-        ValueError."""
+        ValueError.
+        effector_rot (device [T, B, E, 3, 3] float32, row-major rotations, effectors in node order as in
+        targets) with effector_rot_weight (a scalar or E host values, each finite and >= 0): orientation
+        targets per effector (ikpso_solve_track_frames), for unmasked Euler chains and trees.  Every
+        fitness then carries, added last, sum_e eff_w[e] * effector_rot_weight[e] * |R_e -
+        effector_rot[e]|_F^2, R_e the world rotation of effector e's node frame; an effector of weight 0
+        stays position-only.  Served is a FAST solver without axis mask or colliders on the resident
+        family; every other solver raises (unsupported configuration).  With every weight 0 (or
+        effector_rot_weight=None) the answers equal the call without the term, bit for bit.  Not
+        combined with target_rot or aim_dir (ValueError)."""
         torch = _torch()
         if target_rot is not None and aim_dir is not None:
             raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
+        frames_form = effector_rot is not None or effector_rot_weight is not None
+        if frames_form and (target_rot is not None or aim_dir is not None):
+            raise ValueError("effector_rot is not combined with target_rot or aim_dir: pass one or the other")
         if targets is None or targets.dim() != 4:
             raise ValueError(f"targets must be [T, B, {self.effectors}, 3]")
         T, B = int(targets.shape[0]), int(targets.shape[1])
@@ -423,6 +474,10 @@ class BatchSolver:
         if aim_dir is not None:
             self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, T, it, stop,
                             (angles, fitness, res, iters), stream)
+            return angles, fitness, res, iters
+        if frames_form:
+            self._solve_frames(targets, effector_rot, effector_rot_weight,
+                               start_pose, B, T, it, stop, (angles, fitness, res, iters), stream)
             return angles, fitness, res, iters
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
