@@ -438,6 +438,55 @@ ikpso_status ikpso_solver_evaluate(ikpso_solver* solver, const float* angles, co
                                    const float* rest, int64_t n, float* out_fitness, float* out_positions,
                                    void* stream);
 
+/* ikpso_solver_evaluate with the node rotations, the rotation error per effector and the
+ * rotation term of ikpso_solve_track_frames in the fitness (added after ABI 5; detect by
+ * symbol): what the orientation entries optimise, reported for given angle vectors.
+ *   angles, targets, rest, n, out_fitness, out_positions: exactly ikpso_solver_evaluate's
+ *   (free dimensions under an axis mask, locked axes at the chain's rotation, NULL targets
+ *   the chain's own, always the Euler form of the chain).
+ *   out_rotations  device, [n][J][9] or NULL: the world rotation of the frames of nodes
+ *                  1..J, row-major, as ikpso_solve_track_pose defines it (the origin's
+ *                  Rx Ry Rz, then Rx Ry Rz of every node down the path; links do not
+ *                  turn the frame).  FAST kernels on the hardware sin/cos add back
+ *                  that unit's known amplitude bias (2 depth(k) * 3.23e-8 of node k's
+ *                  rotation, as their link lengths carry it), so the matrices are
+ *                  orthonormal to float32 rounding; out_rot_error and the term are
+ *                  formed on the rotation returned here.
+ *   target_rot     device, [n][E][9] or NULL: one row-major rotation per vector and
+ *                  effector, effectors in node order as targets indexes them; used as
+ *                  given.
+ *   out_rot_error  device, [n][E] or NULL: the unweighted |R_{k_e} - target_rot[e]|_F^2
+ *                  of every effector, the nine squared differences accumulated in
+ *                  row-major order.  The value is 4 (1 - cos theta) for the geodesic
+ *                  angle theta, with no weight in the way.  Needs target_rot.
+ *   rot_weights    HOST memory (as in ikpso_solve_track_frames), E floats read during
+ *                  the call, each finite and >= 0; NULL: all 0.
+ * out_fitness is ikpso_solver_evaluate's fitness plus, accumulated over the effectors in
+ * node order and added last,
+ *   sum_e effector_weight[k_e] * rot_weights[e] * |R_{k_e} - target_rot[e]|_F^2
+ * -- ikpso_solve_track_frames' expression, and for a folded arm (E = 1) also
+ * ikpso_solve_track_pose's with orientation_weight = rot_weights[0] (the folded kernels
+ * compute it in their own form: agreement is within the FAST tolerance, as for
+ * ikpso_solver_evaluate).  A weight of 0 contributes nothing, and that effector's target
+ * is never read into the sum.  A fitness the collider term set to FLT_MAX stays FLT_MAX.
+ * With every weight 0 (or NULL) out_fitness and out_positions are ikpso_solver_evaluate's:
+ * the same expressions in another kernel, so in REFERENCE arithmetic, where every
+ * rounding is pinned, the same values; in FAST they may differ by the rounding any two
+ * FAST builds differ by (FMA contraction is the compiler's, kernel by kernel).
+ * Served is every solver ikpso_solver_evaluate serves -- FAST and REFERENCE, masked
+ * chains, folded DH arms (through their Euler chain), trees, chains with colliders, every
+ * compiled topology -- routed as evaluate routes it (a chain whose solve runs the masked
+ * collider arithmetic is evaluated by it).  Nothing evaluate accepts is refused.
+ * IKPSO_ERR_INVALID_ARG: what ikpso_solver_evaluate rejects; a NaN, infinite or negative
+ * weight; some weight > 0 with a NULL target_rot; out_rot_error with a NULL target_rot.
+ * n == 0 is IKPSO_OK with no device work.  Stream-ordered: the call does not
+ * synchronise (the weights are read during the call), and like ikpso_solver_evaluate it
+ * neither waits for nor settles a pending solve. */
+ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* solver, const float* angles, const float* targets,
+                                          const float* rest, const float* target_rot, const float* rot_weights,
+                                          int64_t n, float* out_fitness, float* out_positions,
+                                          float* out_rotations, float* out_rot_error, void* stream);
+
 /* Copy the generator states of local swarms [first_swarm, first_swarm + count)
  * (P states each, swarm-major, 48-byte curandState layout) into dst (any memory,
  * count * P states), after settling a pending solve (ABI >= 5).  Synchronises

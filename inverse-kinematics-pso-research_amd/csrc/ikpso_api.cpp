@@ -1108,6 +1108,32 @@ ikpso_status ikpso_solver_evaluate(ikpso_solver* s, const float* angles, const f
     return IKPSO_OK;
 }
 
+// ikpso_solver_evaluate on the kernels that keep the node rotations: every solver evaluate serves, the
+// rotation term of ikpso_solve_track_frames in the fitness.  The weights go by value (EvalFramesIO::rot_w).
+ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* s, const float* angles, const float* targets,
+                                          const float* rest, const float* target_rot, const float* rot_weights,
+                                          int64_t n, float* out_fitness, float* out_positions, float* out_rotations,
+                                          float* out_rot_error, void* stream)
+{
+    if (!s || n < 0 || (n > 0 && !angles)) return IKPSO_ERR_INVALID_ARG;
+    EvalFramesIO io{};
+    io.e = EvalIO{angles, targets, rest, out_fitness, out_positions, n};
+    bool weighted = false;
+    const int E = s->chain.E;
+    for (int e = 0; rot_weights && e < E; ++e) {
+        const float w = rot_weights[e];
+        if (!(w >= 0.0f) || w > FLT_MAX) return IKPSO_ERR_INVALID_ARG;  // NaN, negative or infinite
+        if (e < kMaxEffFrames) io.rot_w[e] = w;
+        weighted = weighted || w > 0.0f;
+    }
+    if ((weighted || out_rot_error) && !target_rot) return IKPSO_ERR_INVALID_ARG;
+    io.target_rot = target_rot;
+    io.out_rotations = out_rotations;
+    io.out_rot_error = out_rot_error;
+    IKPSO_HIP(launch_evaluate_frames(s->chain, s->mode, io, (hipStream_t)stream));
+    return IKPSO_OK;
+}
+
 int ikpso_solver_dof(const ikpso_solver* s) { return s ? s->chain.dof() : 0; }
 int ikpso_solver_effectors(const ikpso_solver* s) { return s ? s->chain.E : 0; }
 int ikpso_solver_collider_count(const ikpso_solver* s) { return s ? s->chain.num_coll : 0; }

@@ -102,6 +102,20 @@ struct EvalIO {
     int64_t n;
 };
 
+// Parameters of the evaluate kernel that also reports rotations (ikpso_solver_evaluate_frames): the
+// evaluate kernel's own first, unchanged (k_evaluate keeps its argument block), then the rotation
+// targets, outputs and weights.  The weights travel by value, as SwarmIO::eff_rot_w does.
+struct EvalFramesIO {
+    EvalIO e;
+    const float* target_rot;  // [n][E][9] row-major, or null (no weight > 0 and no out_rot_error)
+    float* out_rotations;     // [n][J][9] row-major world rotation of nodes 1..J, or null
+    float* out_rot_error;     // [n][E] unweighted |R - target|_F^2, or null
+    float rot_w[kMaxEffFrames];  // the caller's weight per effector slot, 0 beyond E
+    // 2 depth(k) eps at k - 1 (kHwTrigAmplitudeBias; run_evaluate_frames fills it): what the builds on the
+    // transcendental unit's sin/cos add back to node k's rotation, as ChainConsts::len_hw does to its link
+    float rot_comp[kMaxEffFrames];
+};
+
 // Threads per workgroup the resident kernel is compiled for, by the kernel's
 // dimension count D: 1024 lanes (16 waves, 4 per SIMD, <= 128 VGPRs) while
 // x/v/pbest of one particle fit (D <= 30), 256 lanes (one wave per SIMD, up to
@@ -258,6 +272,7 @@ hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hip
 hipError_t launch_stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t stream);
 size_t stream_workspace_bytes(int64_t B, int P, int D, bool with_state);
 hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipStream_t stream);
+hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream);
 // Cooperative resident kernel (ikpso_coop.h): io.coop_* describe the grid and workspace.
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream);
 // Co-resident workgroups per CU of the cooperative kernel, CU count, threads per workgroup.

@@ -115,6 +115,14 @@ hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipS
     return launch_on_topology(ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate(ch, mode, io, stream); });
 }
 
+hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream)
+{
+    if (io.e.n <= 0) return hipSuccess;
+    if (!ch.aux_dev) return hipErrorInvalidValue;
+    return launch_on_topology(
+        ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_frames(ch, mode, io, stream); });
+}
+
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)
 {
     if (io.num_swarms <= 0) return hipSuccess;

@@ -1,5 +1,5 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, PoseOps<Topo>, AimOps<Topo> and
-// FramesOps<Topo>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, PoseOps<Topo>, AimOps<Topo>,
+// FramesOps<Topo> and EvalFramesOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
@@ -49,6 +49,12 @@ template <class Topo, int MODE>
 hipError_t ModeOps<Topo, MODE>::evaluate(const ChainHost& ch, const EvalIO& io, hipStream_t s)
 {
     return run_evaluate<Topo, MODE>(ch, io, s);
+}
+
+template <class Topo, int MODE>
+hipError_t EvalFramesOps<Topo, MODE>::evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t s)
+{
+    return run_evaluate_frames<Topo, MODE>(ch, io, s);
 }
 
 template <class Topo, int MODE>

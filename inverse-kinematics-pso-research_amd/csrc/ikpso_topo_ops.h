@@ -47,6 +47,13 @@ struct FramesOps {
     static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
+// The evaluate kernels that also report the node rotations and the rotation error
+// (ikpso_solver_evaluate_frames; every Euler topology, both modes), likewise (ikpso_inst_evalframes_*.hip).
+template <class Topo, int MODE>
+struct EvalFramesOps {
+    static hipError_t evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -98,6 +105,13 @@ struct TopoOps {
     static hipError_t evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipStream_t s)
     {
         return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
+    }
+    static hipError_t evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t s)
+    {
+        if constexpr (Topo::kDH)
+            return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
+        else
+            return with_mode(mode, [&](auto m) { return EvalFramesOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
     static hipError_t coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t s)
     {

@@ -10,7 +10,8 @@ from ._abi import (ARITH_FAST, ARITH_REFERENCE, COLLIDER_DTYPE, NODE, NODE_DTYPE
 from .scene import (RESET_TARGETS, EffectorNode, Node, OriginNode, Scene, TargetNode, check_distance,
                     init_colliders, reference_scene, serial_chain)
 from .solver import (MAIN_FITNESS, MAIN_PSO, BatchSolver, FitnessConfig, PSOConfig, calculate_pso,
-                     init_generators, init_generators_seeded, make_collider, particles_tensor, rng_tensor)
+                     init_generators, init_generators_seeded, make_collider, particles_tensor, rng_tensor,
+                     rotation_angle)
 from .dh import DHArm, dh_arm, dh_forward
 from .workloads import Workload, workload
 
@@ -19,5 +20,5 @@ __all__ = [
     "IkpsoError", "StaleLibraryError", "build_id", "load", "RESET_TARGETS", "EffectorNode", "Node", "OriginNode", "Scene", "TargetNode",
     "check_distance", "reference_scene", "serial_chain", "MAIN_FITNESS", "MAIN_PSO", "BatchSolver",
     "FitnessConfig", "PSOConfig", "calculate_pso", "init_generators", "init_generators_seeded",
-    "particles_tensor", "rng_tensor", "Workload", "workload", "DHArm", "dh_arm", "dh_forward",
+    "particles_tensor", "rng_tensor", "rotation_angle", "Workload", "workload", "DHArm", "dh_arm", "dh_forward",
 ]

@@ -114,6 +114,15 @@ def make_collider(size, pos, quat=(0.0, 0.0, 0.0, 1.0)) -> np.ndarray:
     return c
 
 
+def rotation_angle(rot_error):
+    """Geodesic angle (radians) between two rotations from their squared Frobenius distance
+    |Ra - Rb|_F^2 = 4 (1 - cos theta) -- BatchSolver.evaluate_frames' rot_error: arccos(clip(1 - e / 4,
+    -1, 1)).  A torch tensor gives a tensor, anything else a numpy array."""
+    if hasattr(rot_error, "clamp"):
+        return (1.0 - rot_error / 4.0).clamp(-1.0, 1.0).acos()
+    return np.arccos(np.clip(1.0 - np.asarray(rot_error) / 4.0, -1.0, 1.0))
+
+
 def rng_tensor(count: int, device="cuda"):
     """Device buffer for `count` generator states (48 bytes each, curandState_t layout)."""
     torch = _torch()
@@ -519,6 +528,49 @@ class BatchSolver:
                                                    _dev_ptr(fit), _dev_ptr(pos), _stream_handle(stream)),
                    "ikpso_solver_evaluate")
         return fit, pos
+
+    def evaluate_frames(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None,
+                        stream=None):
+        """evaluate() with the node rotations and the orientation objective (ikpso_solver_evaluate_frames):
+        (fitness [n], node positions [n, J, 3], node rotations [n, J, 3, 3], rot_error [n, E] or None).
+        angles [n, D], targets [n, E, 3] or None and rest [n, D] or None are evaluate()'s.  effector_rot
+        (device [n, E, 3, 3] float32, row-major, effectors in node order as in targets) gives rot_error, the
+        unweighted |R_e - effector_rot[e]|_F^2 per effector (rotation_angle() turns it into the geodesic
+        angle); without it rot_error is None.  effector_rot_weight (a scalar or E host values, each finite
+        and >= 0; None: all 0) adds sum_e eff_w[e] * effector_rot_weight[e] * rot_error[e] to the fitness,
+        last: the fitness solve_track(effector_rot=...) minimises, and with E = 1 the one
+        solve_track(target_rot=..., orientation_weight=...) does.  Every solver evaluate() serves is served."""
+        torch = _torch()
+        n = int(angles.shape[0])
+        E, J = self.effectors, self.chain.shape[0] - 1
+        if tuple(angles.shape) != (n, self.dof):
+            raise ValueError(f"angles must be [n, {self.dof}]")
+        if targets is not None and tuple(targets.shape) != (n, E, 3):
+            raise ValueError(f"targets must be [{n}, {E}, 3]")
+        if rest is not None and tuple(rest.shape) != (n, self.dof):
+            raise ValueError(f"rest must be [{n}, {self.dof}]")
+        if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
+            raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
+        host_w = None  # no weights: every weight 0
+        if effector_rot_weight is not None:
+            w = np.asarray(effector_rot_weight, dtype=np.float32).reshape(-1)
+            if w.size == 1:
+                w = np.repeat(w, E)
+            if w.shape != (E,):
+                raise ValueError(f"effector_rot_weight must be a scalar or hold {E} values")
+            host_w = (ctypes.c_float * E)(*w.tolist())  # read during the call
+        for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
+            self._check_tensor(t, name, angles.device)
+        fit = torch.empty((n,), dtype=torch.float32, device=angles.device)
+        pos = torch.empty((n, J, 3), dtype=torch.float32, device=angles.device)
+        rot = torch.empty((n, J, 3, 3), dtype=torch.float32, device=angles.device)
+        err = None if effector_rot is None else torch.empty((n, E), dtype=torch.float32, device=angles.device)
+        _abi.check(self._lib.ikpso_solver_evaluate_frames(self._h, _dev_ptr(angles), _dev_ptr(targets), _dev_ptr(rest),
+                                                          _dev_ptr(effector_rot), host_w, n, _dev_ptr(fit),
+                                                          _dev_ptr(pos), _dev_ptr(rot), _dev_ptr(err),
+                                                          _stream_handle(stream)),
+                   "ikpso_solver_evaluate_frames")
+        return fit, pos, rot, err
 
     def close(self) -> None:
         if getattr(self, "_h", None):
