@@ -420,6 +420,21 @@ int pick_kernel(const ChainHost& ch, int P, int requested)
     return fits ? IKPSO_KERNEL_RESIDENT : (coop ? IKPSO_KERNEL_COOP : IKPSO_KERNEL_STREAMING);
 }
 
+// The term a track entry adds to every fitness, and so the track kernels it runs: the folded chain's pose
+// kernels (ikpso_solve_track_pose) or aim kernels (ikpso_solve_track_aim), or the Euler topologies'
+// effector-frame kernels (ikpso_solve_track_frames).  None: the plain track kernel.
+struct TrackTerm {
+    enum Kind { kNone, kPose, kAim, kFrames };
+    Kind kind = kNone;
+    bool weighted = false;  // the weight, or some effector's, is > 0 (solve_track_term)
+    // the targets on the device: kPose [frames][B][9] rotations, kAim [frames][B][3] directions,
+    // kFrames [frames][B][E][9] rotations per effector
+    const float* target = nullptr;
+    float weight = 0.0f;                  // kPose, kAim
+    float aim_axis[3] = {};               // kAim: a' = G a (aim_axis_folded)
+    float eff_rot_w[kMaxEffFrames] = {};  // kFrames: the caller's weight per effector
+};
+
 // What one solve launches with (the arguments of the solve entry points).
 struct SolveArgs {
     const float* targets = nullptr;
@@ -430,20 +445,7 @@ struct SolveArgs {
     uint32_t stop_key = 0;              // ikpso_solve_batch_until (0: no stop)
     int32_t* out_iterations = nullptr;
     int32_t frames = 0;  // > 0: ikpso_solve_track, every buffer but start_pose time-major
-    // ikpso_solve_track_pose: the pose track kernels, with the orientation targets [frames][B][9]
-    bool pose = false;
-    const float* target_rot = nullptr;
-    float orientation_weight = 0.0f;
-    // ikpso_solve_track_aim: the aim track kernels, with the directions [frames][B][3] and a' = G a
-    bool aim = false;
-    const float* aim_dir = nullptr;
-    float aim_weight = 0.0f;
-    float aim_axis[3] = {0.0f, 0.0f, 0.0f};
-    // ikpso_solve_track_frames: the effector-frame track kernels, with the rotations [frames][B][E][9] and
-    // the caller's weight per effector
-    bool eff_frames = false;
-    const float* eff_rot = nullptr;
-    float eff_rot_w[kMaxEffFrames] = {};
+    TrackTerm term;      // ikpso_solve_track_pose, _aim, _frames: the term's track kernels
 };
 
 // The kernels the last solve ran, for ikpso_solver_kernel_name.
@@ -531,17 +533,27 @@ SwarmIO swarm_io(const ikpso_solver* s, const SolveArgs& a)
     io.num_swarms = a.num_swarms;
     io.stop_key = a.stop_key;
     io.out_iterations = a.out_iterations;
-    io.pose = a.pose ? 1 : 0;
-    io.target_rot = a.target_rot;
-    io.orient_w = a.orientation_weight;
     for (int i = 0; i < 9; ++i) io.tip_rot[i] = s->solve_chain().tip_rot[i];
-    io.aim = a.aim ? 1 : 0;
-    io.aim_w = a.aim_weight;
-    io.aim_dir = a.aim_dir;
-    for (int i = 0; i < 3; ++i) io.aim_axis[i] = a.aim_axis[i];
-    io.eff_frames = a.eff_frames ? 1 : 0;
-    io.eff_rot = a.eff_rot;
-    for (int i = 0; i < kMaxEffFrames; ++i) io.eff_rot_w[i] = a.eff_rot_w[i];
+    const TrackTerm& t = a.term;
+    switch (t.kind) {  // (the routing ints: launch_resident)
+    case TrackTerm::kNone: break;
+    case TrackTerm::kPose:
+        io.pose = 1;
+        io.target_rot = t.target;
+        io.orient_w = t.weight;
+        break;
+    case TrackTerm::kAim:
+        io.aim = 1;
+        io.aim_dir = t.target;
+        io.aim_w = t.weight;
+        for (int i = 0; i < 3; ++i) io.aim_axis[i] = t.aim_axis[i];
+        break;
+    case TrackTerm::kFrames:
+        io.eff_frames = 1;
+        io.eff_rot = t.target;
+        for (int i = 0; i < kMaxEffFrames; ++i) io.eff_rot_w[i] = t.eff_rot_w[i];
+        break;
+    }
     return io;
 }
 
@@ -633,6 +645,68 @@ ikpso_status begin_solve(ikpso_solver* s, int64_t num_swarms, bool stops)
 
 // ikpso_solve_batch_until's threshold as the kernels compare it (negative: never stop)
 uint32_t stop_key_of(float stop_fitness) { return stop_fitness < 0.0f ? 0u : ordered_key_host(stop_fitness); }
+
+// The caller's weight per effector (rot_weights: E host values, or null for every weight 0) into the
+// kernels' kMaxEffFrames slots.  False: a weight is NaN, negative or infinite.  *any: some weight is > 0,
+// one beyond the slots included.
+bool effector_weights(const float* rot_weights, int E, float (&slots)[kMaxEffFrames], bool* any)
+{
+    *any = false;
+    for (int e = 0; rot_weights && e < E; ++e) {
+        const float w = rot_weights[e];
+        if (!(w >= 0.0f) || w > FLT_MAX) return false;
+        if (e < kMaxEffFrames) slots[e] = w;
+        *any = *any || w > 0.0f;
+    }
+    return true;
+}
+
+// What the four track entries share, and the order of their answers (DESIGN, "The track entries' status
+// ladder"): every invalid argument, the common ones here and then the entry's own; a solver the entry does
+// not serve; the empty call; then begin_solve and the launch.  term_checks(term) is the entry's part: it
+// fills the term in and returns IKPSO_ERR_INVALID_ARG, or IKPSO_ERR_UNSUPPORTED when nothing else is
+// wrong but the solver has no kernel with the term, or IKPSO_OK.
+// The frame loop of ikpso_solve_batch_until calls in one call.  Resident family: one launch, the loop
+// inside the kernel (swarm_track_body).  Streaming (the plain entry alone; also for a solver AUTO routed
+// to the cooperative family, as in solve_batch_until): the loop here, one streaming solve per frame over
+// pointer offsets, so the contract holds by construction.
+template <class TermChecks>
+ikpso_status solve_track_term(ikpso_solver* s, const float* targets, const float* start_pose, int64_t num_swarms,
+                              int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
+                              float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream,
+                              TermChecks&& term_checks)
+{
+    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
+        return IKPSO_ERR_INVALID_ARG;
+    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
+    SolveArgs all{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
+                  out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
+    ikpso_status st = term_checks(all.term);
+    if (st != IKPSO_OK) return st;
+    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
+    if ((st = begin_solve(s, num_swarms, true)) != IKPSO_OK) return st;
+    // Weight 0 (every weight 0) is the term absent: the plain track kernel computes that fitness, and only
+    // it gives ikpso_solve_track's bits.  A term's kernel evaluates the same position expressions, but the
+    // compiler contracts an a*b + c*d of them into an FMA the other way round here and there (the kernels'
+    // contraction is not pinned), an ulp away.
+    if (!all.term.weighted) all.term = TrackTerm{};
+    if (all.term.kind == TrackTerm::kFrames) s->last = kRouteFrames;
+    const hipStream_t hs = (hipStream_t)stream;
+    if (s->last != kRouteStream) return solve_resident(s, all, hs);
+    const int64_t B = num_swarms, nt = B * s->chain.E * 3, na = B * s->chain.dof();  // one frame of targets, of angles
+    for (int64_t t = 0; t < frames && st == IKPSO_OK; ++t) {
+        SolveArgs a = all;
+        a.frames = 0;
+        a.targets = targets + t * nt;
+        a.start_pose = t ? out_angles + (t - 1) * na : start_pose;
+        a.out_angles = out_angles + t * na;
+        if (out_fitness) a.out_fitness = out_fitness + t * B;
+        if (out_residual) a.out_residual = out_residual + t * B;
+        if (out_iterations) a.out_iterations = out_iterations + t * B;
+        st = solve_streaming(s, a, hs);
+    }
+    return st;
+}
 
 }  // namespace
 
@@ -903,37 +977,13 @@ ikpso_status ikpso_solve_batch_until(ikpso_solver* s, const float* targets, cons
                                    : solve_resident(s, a, (hipStream_t)stream);
 }
 
-// The frame loop of ikpso_solve_batch_until calls in one call.  Resident family: one launch,
-// the loop inside the kernel (swarm_track_body).  Streaming (also for a solver AUTO routed to
-// the cooperative family, as in solve_batch_until): the loop here, one streaming solve per
-// frame over pointer offsets, so the contract holds by construction.
 ikpso_status ikpso_solve_track(ikpso_solver* s, const float* targets, const float* start_pose, int64_t num_swarms,
                                int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
                                float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
 {
-    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
-        return IKPSO_ERR_INVALID_ARG;
-    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
-    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
-    ikpso_status st = begin_solve(s, num_swarms, true);
-    if (st != IKPSO_OK) return st;
-    const hipStream_t hs = (hipStream_t)stream;
-    const SolveArgs all{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
-                        out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
-    if (s->last != kRouteStream) return solve_resident(s, all, hs);
-    const int64_t B = num_swarms, nt = B * s->chain.E * 3, na = B * s->chain.dof();  // one frame of targets, of angles
-    for (int64_t t = 0; t < frames && st == IKPSO_OK; ++t) {
-        SolveArgs a = all;
-        a.frames = 0;
-        a.targets = targets + t * nt;
-        a.start_pose = t ? out_angles + (t - 1) * na : start_pose;
-        a.out_angles = out_angles + t * na;
-        if (out_fitness) a.out_fitness = out_fitness + t * B;
-        if (out_residual) a.out_residual = out_residual + t * B;
-        if (out_iterations) a.out_iterations = out_iterations + t * B;
-        st = solve_streaming(s, a, hs);
-    }
-    return st;
+    return solve_track_term(s, targets, start_pose, num_swarms, frames, max_iterations, stop_fitness, out_angles,
+                            out_fitness, out_residual, out_iterations, stream,
+                            [](TrackTerm&) { return IKPSO_OK; });
 }
 
 // ikpso_solve_track on the folded chain's pose kernels: the same frame loop in one launch, the
@@ -943,25 +993,16 @@ ikpso_status ikpso_solve_track_pose(ikpso_solver* s, const float* targets, const
                                     int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
                                     float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
 {
-    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
-        return IKPSO_ERR_INVALID_ARG;
-    if (!(orientation_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
-    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
-    if (orientation_weight > 0.0f && !target_rot) return IKPSO_ERR_INVALID_ARG;
-    if (!s->use_dh || s->family != IKPSO_KERNEL_RESIDENT) return IKPSO_ERR_UNSUPPORTED;
-    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
-    const ikpso_status st = begin_solve(s, num_swarms, true);
-    if (st != IKPSO_OK) return st;
-    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
-                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
-    // Weight 0 is the term absent: the plain track kernel computes that fitness, and only it gives
-    // ikpso_solve_track's bits.  A pose kernel evaluates the same position expressions, but the compiler
-    // contracts an a*b + c*d of them into an FMA the other way round here and there (the kernels'
-    // contraction is not pinned), an ulp away.
-    a.pose = orientation_weight > 0.0f;
-    a.target_rot = target_rot;
-    a.orientation_weight = orientation_weight;
-    return solve_resident(s, a, (hipStream_t)stream);
+    return solve_track_term(s, targets, start_pose, num_swarms, frames, max_iterations, stop_fitness, out_angles,
+                            out_fitness, out_residual, out_iterations, stream, [&](TrackTerm& term) {
+        if (!(orientation_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
+        if (orientation_weight > 0.0f && !target_rot) return IKPSO_ERR_INVALID_ARG;
+        term.kind = TrackTerm::kPose;
+        term.weighted = orientation_weight > 0.0f;
+        term.target = target_rot;
+        term.weight = orientation_weight;
+        return s->use_dh && s->family == IKPSO_KERNEL_RESIDENT ? IKPSO_OK : IKPSO_ERR_UNSUPPORTED;
+    });
 }
 
 // ikpso_solve_track on the folded chain's aim kernels: the pose entry's routing and refusals, the
@@ -971,23 +1012,17 @@ ikpso_status ikpso_solve_track_aim(ikpso_solver* s, const float* targets, const 
                                    int32_t max_iterations, float stop_fitness, float* out_angles, float* out_fitness,
                                    float* out_residual, int32_t* out_iterations, void* stream)
 {
-    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
-        return IKPSO_ERR_INVALID_ARG;
-    if (!(aim_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
-    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
-    if (aim_weight > 0.0f && (!aim_dir || !aim_axis)) return IKPSO_ERR_INVALID_ARG;
-    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
-                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
-    // Weight 0 is the term absent: the plain track kernel, as in ikpso_solve_track_pose
-    a.aim = aim_weight > 0.0f;
-    if (a.aim && !aim_axis_folded(s->solve_chain(), aim_axis, a.aim_axis)) return IKPSO_ERR_INVALID_ARG;
-    if (!s->use_dh || s->family != IKPSO_KERNEL_RESIDENT) return IKPSO_ERR_UNSUPPORTED;
-    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
-    const ikpso_status st = begin_solve(s, num_swarms, true);
-    if (st != IKPSO_OK) return st;
-    a.aim_dir = aim_dir;
-    a.aim_weight = aim_weight;
-    return solve_resident(s, a, (hipStream_t)stream);
+    return solve_track_term(s, targets, start_pose, num_swarms, frames, max_iterations, stop_fitness, out_angles,
+                            out_fitness, out_residual, out_iterations, stream, [&](TrackTerm& term) {
+        if (!(aim_weight >= 0.0f)) return IKPSO_ERR_INVALID_ARG;  // negative or NaN
+        if (aim_weight > 0.0f && (!aim_dir || !aim_axis)) return IKPSO_ERR_INVALID_ARG;
+        term.kind = TrackTerm::kAim;
+        term.weighted = aim_weight > 0.0f;
+        if (term.weighted && !aim_axis_folded(s->solve_chain(), aim_axis, term.aim_axis)) return IKPSO_ERR_INVALID_ARG;
+        term.target = aim_dir;
+        term.weight = aim_weight;
+        return s->use_dh && s->family == IKPSO_KERNEL_RESIDENT ? IKPSO_OK : IKPSO_ERR_UNSUPPORTED;
+    });
 }
 
 // ikpso_solve_track on the Euler topologies' effector-frame kernels: the same frame loop in one launch,
@@ -998,35 +1033,19 @@ ikpso_status ikpso_solve_track_frames(ikpso_solver* s, const float* targets, con
                                       int32_t frames, int32_t max_iterations, float stop_fitness, float* out_angles,
                                       float* out_fitness, float* out_residual, int32_t* out_iterations, void* stream)
 {
-    if (!s || num_swarms < 0 || frames < 0 || max_iterations < 0 || stop_fitness != stop_fitness)
-        return IKPSO_ERR_INVALID_ARG;
-    if (frames > 0 && (!targets || !out_angles)) return IKPSO_ERR_INVALID_ARG;
-    SolveArgs a{targets,     start_pose,   num_swarms,           max_iterations, out_angles,
-                out_fitness, out_residual, stop_key_of(stop_fitness), out_iterations, frames};
-    const int E = s->chain.E;
-    for (int e = 0; rot_weights && e < E; ++e) {
-        const float w = rot_weights[e];
-        if (!(w >= 0.0f) || w > FLT_MAX) return IKPSO_ERR_INVALID_ARG;  // NaN, negative or infinite
-        if (e < kMaxEffFrames) a.eff_rot_w[e] = w;
-        a.eff_frames = a.eff_frames || w > 0.0f;
-    }
-    if (a.eff_frames && !target_rot) return IKPSO_ERR_INVALID_ARG;
-    // the refusal ladder: REFERENCE arithmetic; any axis mask (folded, or kept by IKPSO_FLAG_NO_FOLD); a
-    // collider term the kernels test (or their polynomial sin/cos); another family than the resident one
-    const ChainHost& ch = s->chain;
-    if (s->mode != IKPSO_ARITH_FAST || s->use_dh || ch.masked || ch.num_coll > 0 || ch.poly_trig ||
-        s->family != IKPSO_KERNEL_RESIDENT || E > kMaxEffFrames)
-        return IKPSO_ERR_UNSUPPORTED;
-    if (num_swarms == 0 || frames == 0) return IKPSO_OK;
-    const ikpso_status st = begin_solve(s, num_swarms, true);
-    if (st != IKPSO_OK) return st;
-    // Every weight 0 is the term absent: the plain track kernel computes that fitness, and only it gives
-    // ikpso_solve_track's bits (as in ikpso_solve_track_pose).
-    if (a.eff_frames) {
-        a.eff_rot = target_rot;
-        s->last = kRouteFrames;
-    }
-    return solve_resident(s, a, (hipStream_t)stream);
+    return solve_track_term(s, targets, start_pose, num_swarms, frames, max_iterations, stop_fitness, out_angles,
+                            out_fitness, out_residual, out_iterations, stream, [&](TrackTerm& term) {
+        const ChainHost& ch = s->chain;
+        term.kind = TrackTerm::kFrames;
+        if (!effector_weights(rot_weights, ch.E, term.eff_rot_w, &term.weighted)) return IKPSO_ERR_INVALID_ARG;
+        if (term.weighted && !target_rot) return IKPSO_ERR_INVALID_ARG;
+        term.target = target_rot;
+        // the refusal ladder: REFERENCE arithmetic; any axis mask (folded, or kept by IKPSO_FLAG_NO_FOLD); a
+        // collider term the kernels test (or their polynomial sin/cos); another family than the resident one
+        const bool served = s->mode == IKPSO_ARITH_FAST && !s->use_dh && !ch.masked && ch.num_coll == 0 &&
+                            !ch.poly_trig && s->family == IKPSO_KERNEL_RESIDENT && ch.E <= kMaxEffFrames;
+        return served ? IKPSO_OK : IKPSO_ERR_UNSUPPORTED;
+    });
 }
 
 // ordered_key_host / key_to_float, for the tests (not part of the declared ABI)
@@ -1119,13 +1138,7 @@ ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* s, const float* angles, 
     EvalFramesIO io{};
     io.e = EvalIO{angles, targets, rest, out_fitness, out_positions, n};
     bool weighted = false;
-    const int E = s->chain.E;
-    for (int e = 0; rot_weights && e < E; ++e) {
-        const float w = rot_weights[e];
-        if (!(w >= 0.0f) || w > FLT_MAX) return IKPSO_ERR_INVALID_ARG;  // NaN, negative or infinite
-        if (e < kMaxEffFrames) io.rot_w[e] = w;
-        weighted = weighted || w > 0.0f;
-    }
+    if (!effector_weights(rot_weights, s->chain.E, io.rot_w, &weighted)) return IKPSO_ERR_INVALID_ARG;
     if ((weighted || out_rot_error) && !target_rot) return IKPSO_ERR_INVALID_ARG;
     io.target_rot = target_rot;
     io.out_rotations = out_rotations;

@@ -3,8 +3,8 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct AimOps<TopoDH<3>>;
-template struct AimOps<TopoDH<4>>;
-template struct AimOps<TopoDH<5>>;
+template struct TermTrackOps<kTermAim, TopoDH<3>>;
+template struct TermTrackOps<kTermAim, TopoDH<4>>;
+template struct TermTrackOps<kTermAim, TopoDH<5>>;
 #endif
 }  // namespace ikpso

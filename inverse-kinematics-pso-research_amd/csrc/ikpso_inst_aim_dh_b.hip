@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct AimOps<TopoDH<6>>;
-template struct AimOps<TopoDH<7>>;
+template struct TermTrackOps<kTermAim, TopoDH<6>>;
+template struct TermTrackOps<kTermAim, TopoDH<7>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct AimOps<TopoDH<8>>;
-template struct AimOps<TopoDH<9>>;
+template struct TermTrackOps<kTermAim, TopoDH<8>>;
+template struct TermTrackOps<kTermAim, TopoDH<9>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct AimOps<TopoDH<10>>;
-template struct AimOps<TopoDH<11>>;
+template struct TermTrackOps<kTermAim, TopoDH<10>>;
+template struct TermTrackOps<kTermAim, TopoDH<11>>;
 #endif
 }  // namespace ikpso

@@ -3,6 +3,6 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct AimOps<TopoDH<12>>;
+template struct TermTrackOps<kTermAim, TopoDH<12>>;
 #endif
 }  // namespace ikpso

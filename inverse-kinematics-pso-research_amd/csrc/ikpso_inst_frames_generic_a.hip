@@ -3,13 +3,13 @@
 
 namespace ikpso {
 #if IKPSO_WITH_OTHERS
-template struct FramesOps<TopoGeneric<1>>;
-template struct FramesOps<TopoGeneric<2>>;
-template struct FramesOps<TopoGeneric<3>>;
-template struct FramesOps<TopoGeneric<4>>;
-template struct FramesOps<TopoGeneric<5>>;
-template struct FramesOps<TopoGeneric<6>>;
-template struct FramesOps<TopoGeneric<7>>;
-template struct FramesOps<TopoGeneric<8>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<1>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<2>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<3>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<4>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<5>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<6>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<7>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<8>>;
 #endif
 }  // namespace ikpso

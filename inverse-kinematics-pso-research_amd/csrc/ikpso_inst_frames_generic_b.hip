@@ -3,9 +3,9 @@
 
 namespace ikpso {
 #if IKPSO_WITH_OTHERS
-template struct FramesOps<TopoGeneric<9>>;
-template struct FramesOps<TopoGeneric<10>>;
-template struct FramesOps<TopoGeneric<11>>;
-template struct FramesOps<TopoGeneric<12>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<9>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<10>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<11>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<12>>;
 #endif
 }  // namespace ikpso

@@ -3,9 +3,9 @@
 
 namespace ikpso {
 #if IKPSO_WITH_OTHERS
-template struct FramesOps<TopoGeneric<13>>;
-template struct FramesOps<TopoGeneric<14>>;
-template struct FramesOps<TopoGeneric<15>>;
-template struct FramesOps<TopoGeneric<16>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<13>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<14>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<15>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<16>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_OTHERS
-template struct FramesOps<TopoGeneric<17>>;
-template struct FramesOps<TopoGeneric<18>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<17>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<18>>;
 #endif
 }  // namespace ikpso

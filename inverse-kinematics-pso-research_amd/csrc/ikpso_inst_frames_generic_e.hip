@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_OTHERS
-template struct FramesOps<TopoGeneric<19>>;
-template struct FramesOps<TopoGeneric<20>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<19>>;
+template struct TermTrackOps<kTermOrient, TopoGeneric<20>>;
 #endif
 }  // namespace ikpso

@@ -3,6 +3,6 @@
 
 namespace ikpso {
 #if IKPSO_WITH_REF7
-template struct FramesOps<TopoRef7>;
+template struct TermTrackOps<kTermOrient, TopoRef7>;
 #endif
 }  // namespace ikpso

@@ -3,6 +3,6 @@
 
 namespace ikpso {
 #if IKPSO_WITH_SERIAL20
-template struct FramesOps<TopoSerialTip<20>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<20>>;
 #endif
 }  // namespace ikpso

@@ -3,8 +3,8 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct FramesOps<TopoSerialTip<6>>;
-template struct FramesOps<TopoSerialTip<7>>;
-template struct FramesOps<TopoSerialTip<8>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<6>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<7>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<8>>;
 #endif
 }  // namespace ikpso

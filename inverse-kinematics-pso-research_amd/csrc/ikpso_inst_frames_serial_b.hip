@@ -3,8 +3,8 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct FramesOps<TopoSerialTip<9>>;
-template struct FramesOps<TopoSerialTip<10>>;
-template struct FramesOps<TopoSerialTip<11>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<9>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<10>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<11>>;
 #endif
 }  // namespace ikpso

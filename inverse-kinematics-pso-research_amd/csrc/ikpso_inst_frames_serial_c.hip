@@ -3,8 +3,8 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct FramesOps<TopoSerialTip<12>>;
-template struct FramesOps<TopoSerialTip<13>>;
-template struct FramesOps<TopoSerialTip<14>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<12>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<13>>;
+template struct TermTrackOps<kTermOrient, TopoSerialTip<14>>;
 #endif
 }  // namespace ikpso

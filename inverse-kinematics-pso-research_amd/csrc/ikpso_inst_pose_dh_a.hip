@@ -3,8 +3,8 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct PoseOps<TopoDH<3>>;
-template struct PoseOps<TopoDH<4>>;
-template struct PoseOps<TopoDH<5>>;
+template struct TermTrackOps<kTermOrient, TopoDH<3>>;
+template struct TermTrackOps<kTermOrient, TopoDH<4>>;
+template struct TermTrackOps<kTermOrient, TopoDH<5>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct PoseOps<TopoDH<6>>;
-template struct PoseOps<TopoDH<7>>;
+template struct TermTrackOps<kTermOrient, TopoDH<6>>;
+template struct TermTrackOps<kTermOrient, TopoDH<7>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct PoseOps<TopoDH<8>>;
-template struct PoseOps<TopoDH<9>>;
+template struct TermTrackOps<kTermOrient, TopoDH<8>>;
+template struct TermTrackOps<kTermOrient, TopoDH<9>>;
 #endif
 }  // namespace ikpso

@@ -3,7 +3,7 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct PoseOps<TopoDH<10>>;
-template struct PoseOps<TopoDH<11>>;
+template struct TermTrackOps<kTermOrient, TopoDH<10>>;
+template struct TermTrackOps<kTermOrient, TopoDH<11>>;
 #endif
 }  // namespace ikpso

@@ -3,6 +3,6 @@
 
 namespace ikpso {
 #if IKPSO_WITH_DH
-template struct PoseOps<TopoDH<12>>;
+template struct TermTrackOps<kTermOrient, TopoDH<12>>;
 #endif
 }  // namespace ikpso

@@ -197,14 +197,21 @@ constexpr float kHwTrigMaxAbs = 100.0f;
 // (profiles/r06/hwtrig_comp.txt).  Per value no fp32 correction exists (1 + eps
 // rounds back to 1); per link the scaled length is representable.
 constexpr double kHwTrigAmplitudeBias = 3.23e-8;
+// depth[k]: the nodes from the root's child down to node k (depth[0] = 0), which is how many nodes' plane
+// rotations node k's link and frame pass (len_hw below, EvalFramesIO::rot_comp).
+template <int J>
+inline void node_depths(const ChainHost& h, int (&depth)[J + 1])
+{
+    depth[0] = 0;
+    for (int k = 1; k <= J; ++k) depth[k] = (h.parent[k] > 0 ? depth[h.parent[k]] : 0) + 1;
+}
 template <int J>
 ChainConsts<J> make_consts(const ChainHost& h)
 {
     ChainConsts<J> c;
     memset(&c, 0, sizeof(c));
     int depth[J + 1];
-    depth[0] = 0;
-    for (int k = 1; k <= J; ++k) depth[k] = (h.parent[k] > 0 ? depth[h.parent[k]] : 0) + 1;
+    node_depths<J>(h, depth);
     for (int k = 0; k <= J; ++k) {
         c.len[k] = h.len[k];
         c.len_hw[k] = k ? (float)((double)h.len[k] * (1.0 + 2.0 * depth[k] * kHwTrigAmplitudeBias)) : h.len[k];

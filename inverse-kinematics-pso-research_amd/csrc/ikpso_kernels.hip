@@ -98,13 +98,20 @@ hipError_t launch_resident(const ChainHost& ch, int mode, const SwarmIO& io, hip
     if (io.num_swarms <= 0) return hipSuccess;
     if (!ch.aux_dev) return hipErrorInvalidValue;  // the kernels read aux for the optional terms
     const int block = ((io.P + 63) / 64) * 64;
+    // the term the host routed the launch to (ikpso_solve_track_pose and ikpso_solve_track_frames: the
+    // orientation term of their topologies; ikpso_solve_track_aim), or none
+    const int term = io.pose || io.eff_frames ? kTermOrient : io.aim ? kTermAim : 0;
     return launch_on_topology(ch, [&](auto topo) {
         using T = decltype(topo);
-        if (io.pose) return TopoOps<T>::pose_track(ch, mode, io, block, stream);  // (ikpso_solve_track_pose)
-        if (io.aim) return TopoOps<T>::aim_track(ch, mode, io, block, stream);    // (ikpso_solve_track_aim)
-        if (io.eff_frames) return TopoOps<T>::frames_track(ch, mode, io, block, stream);  // (ikpso_solve_track_frames)
-        return io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
-                             : TopoOps<T>::resident(ch, mode, io, block, stream);
+        switch (term) {
+        case kTermOrient:
+            if ((io.pose != 0) != T::kDH) return hipErrorNotSupported;  // the tip's term: the folded chain alone
+            return TopoOps<T>::template term_track<kTermOrient>(ch, mode, io, block, stream);
+        case kTermAim: return TopoOps<T>::template term_track<kTermAim>(ch, mode, io, block, stream);
+        default:
+            return io.frames > 0 ? TopoOps<T>::track(ch, mode, io, block, stream)  // (ikpso_solve_track)
+                                 : TopoOps<T>::resident(ch, mode, io, block, stream);
+        }
     });
 }
 

@@ -945,49 +945,51 @@ inline hipError_t run_resident(const ChainHost& ch, const SwarmIO& io, int block
     });
 }
 
-// The pose track kernels (ikpso_solve_track_pose): the folded chain's track builds with the
-// orientation term, one per term set the folded track kernel has (dh_terms).
-template <class Topo>
-inline hipError_t run_resident_pose(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
+// The track kernels with a term of their own, FAST: TERM beside the term set of the track build it
+// extends.  The folded chain (ikpso_solve_track_pose: kTermOrient, ikpso_solve_track_aim: kTermAim) has
+// one per term set its track kernel has (dh_terms).  An Euler topology (ikpso_solve_track_frames:
+// kTermOrient, a rotation term per effector) has the runtime-term build alone: a masked chain, a collider
+// term (or the polynomial sin/cos its builds carry) has no such build, and the host refuses those solvers.
+template <class Topo, int TERM>
+inline hipError_t run_resident_term(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
 {
-    static_assert(Topo::kDH, "the orientation term: the folded chain");
+    static_assert(TERM == kTermOrient || (TERM == kTermAim && Topo::kDH), "the aim term: the folded chain");
+    if constexpr (!Topo::kDH) {
+        if (ch.masked || ch.num_coll > 0 || ch.poly_trig) return hipErrorNotSupported;
+    }
     const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
     const dim3 grid((unsigned)io.num_swarms), threads(block);
-    hipError_t err = hipErrorNotSupported;
-    dh_terms<Topo>(term_set(ch), &err, [&](auto t) {
-        return launch_resident_build<Topo, IKPSO_ARITH_FAST, decltype(t)::value | kTermRev | kTermOrient, true>(
-            cc, io, grid, threads, stream);
-    });
-    return err;
+    if constexpr (Topo::kDH) {
+        hipError_t err = hipErrorNotSupported;
+        dh_terms<Topo>(term_set(ch), &err, [&](auto t) {
+            return launch_resident_build<Topo, IKPSO_ARITH_FAST, decltype(t)::value | kTermRev | TERM, true>(
+                cc, io, grid, threads, stream);
+        });
+        return err;
+    } else {
+        return launch_resident_build<Topo, IKPSO_ARITH_FAST, kTermRuntime | TERM, true>(cc, io, grid, threads, stream);
+    }
 }
 
-// The effector-frame track kernels (ikpso_solve_track_frames): the runtime-term track build of an Euler
-// topology with the rotation term per effector, FAST.  A masked chain, a collider term (or the
-// polynomial sin/cos its builds carry) has no such build: the host refuses those solvers.
-template <class Topo>
-inline hipError_t run_resident_frames(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
+// The evaluate kernels' launch for n vectors: launch(term set, grid, threads) of the build that evaluates
+// the chain.  The mask only places the given angles (no PSO): the unmasked builds evaluate it -- but a chain
+// whose angles reach beyond the transcendental unit's range (poly_trig) is solved by the masked collider
+// builds for their polynomial sin/cos, and is evaluated by the same arithmetic (as one with colliders that
+// are no rotations).
+template <class F>
+inline hipError_t launch_evaluate_build(const ChainHost& ch, int64_t n, F&& launch)
 {
-    static_assert(!Topo::kDH, "the effector rotation term: the Euler topologies");
-    if (ch.masked || ch.num_coll > 0 || ch.poly_trig) return hipErrorNotSupported;
-    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
-    const dim3 grid((unsigned)io.num_swarms), threads(block);
-    return launch_resident_build<Topo, IKPSO_ARITH_FAST, kTermRuntime | kTermOrient, true>(cc, io, grid, threads,
-                                                                                          stream);
-}
-
-// The aim track kernels (ikpso_solve_track_aim): the same ladder with the tool-axis term.
-template <class Topo>
-inline hipError_t run_resident_aim(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream)
-{
-    static_assert(Topo::kDH, "the aim term: the folded chain");
-    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
-    const dim3 grid((unsigned)io.num_swarms), threads(block);
-    hipError_t err = hipErrorNotSupported;
-    dh_terms<Topo>(term_set(ch), &err, [&](auto t) {
-        return launch_resident_build<Topo, IKPSO_ARITH_FAST, decltype(t)::value | kTermRev | kTermAim, true>(
-            cc, io, grid, threads, stream);
-    });
-    return err;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    if (blocks < 1) blocks = 1;
+    const dim3 grid((unsigned)blocks), threads(256);
+    if ((ch.poly_trig && IKPSO_COLLIDE_HW_TRIG) || (ch.num_coll > 0 && !ch.coll_obb))
+        launch(std::integral_constant<int, kTermRuntime | kTermColliders | kTermMask>{}, grid, threads);
+    else if (ch.num_coll > 0)
+        launch(std::integral_constant<int, kTermRuntime | kTermColliders>{}, grid, threads);
+    else
+        launch(std::integral_constant<int, kTermRuntime>{}, grid, threads);
+    return hipGetLastError();
 }
 
 template <class Topo, int MODE>
@@ -996,53 +998,26 @@ inline hipError_t run_evaluate(const ChainHost& ch, const EvalIO& io, hipStream_
     if constexpr (Topo::kDH) {  // the solver evaluates through its Euler chain
         return hipErrorNotSupported;
     } else {
-    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
-    int64_t blocks = (io.n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    // the mask only places the given angles (no PSO): the unmasked builds evaluate it -- but a chain whose
-    // angles reach beyond the transcendental unit's range (poly_trig) is solved by the masked collider
-    // builds for their polynomial sin/cos, and is evaluated by the same arithmetic
-    if ((ch.poly_trig && IKPSO_COLLIDE_HW_TRIG) || (ch.num_coll > 0 && !ch.coll_obb))
-        hipLaunchKernelGGL((k_evaluate<Topo, MODE, kTermRuntime | kTermColliders | kTermMask>), dim3((unsigned)blocks),
-                           dim3(256), 0, stream, cc, io);
-    else if (ch.num_coll > 0)
-        hipLaunchKernelGGL((k_evaluate<Topo, MODE, kTermRuntime | kTermColliders>), dim3((unsigned)blocks), dim3(256),
-                           0, stream, cc, io);
-    else
-        hipLaunchKernelGGL((k_evaluate<Topo, MODE, kTermRuntime>), dim3((unsigned)blocks), dim3(256), 0, stream, cc,
-                           io);
-    return hipGetLastError();
+        const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
+        return launch_evaluate_build(ch, io.n, [&](auto t, dim3 grid, dim3 threads) {
+            hipLaunchKernelGGL((k_evaluate<Topo, MODE, decltype(t)::value>), grid, threads, 0, stream, cc, io);
+        });
     }
 }
 
-// ikpso_solver_evaluate_frames: run_evaluate's grid and routing rule (a poly_trig chain, or one with
-// colliders that are no rotations, takes the masked collider arithmetic its solve ran), on the sibling kernel.
+// ikpso_solver_evaluate_frames: run_evaluate's grid and routing rule on the sibling kernel.
 template <class Topo, int MODE>
 inline hipError_t run_evaluate_frames(const ChainHost& ch, const EvalFramesIO& caller_io, hipStream_t stream)
 {
     static_assert(!Topo::kDH, "the solver evaluates through its Euler chain");
     const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
     EvalFramesIO io = caller_io;
-    int depth[Topo::J + 1];  // (as make_consts takes it for len_hw)
-    depth[0] = 0;
-    for (int k = 1; k <= Topo::J; ++k) {
-        depth[k] = (ch.parent[k] > 0 ? depth[ch.parent[k]] : 0) + 1;
-        io.rot_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
-    }
-    int64_t blocks = (io.e.n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (blocks < 1) blocks = 1;
-    if ((ch.poly_trig && IKPSO_COLLIDE_HW_TRIG) || (ch.num_coll > 0 && !ch.coll_obb))
-        hipLaunchKernelGGL((k_evaluate_frames<Topo, MODE, kTermRuntime | kTermColliders | kTermMask>),
-                           dim3((unsigned)blocks), dim3(256), 0, stream, cc, io);
-    else if (ch.num_coll > 0)
-        hipLaunchKernelGGL((k_evaluate_frames<Topo, MODE, kTermRuntime | kTermColliders>), dim3((unsigned)blocks),
-                           dim3(256), 0, stream, cc, io);
-    else
-        hipLaunchKernelGGL((k_evaluate_frames<Topo, MODE, kTermRuntime>), dim3((unsigned)blocks), dim3(256), 0, stream,
-                           cc, io);
-    return hipGetLastError();
+    int depth[Topo::J + 1];
+    node_depths<Topo::J>(ch, depth);
+    for (int k = 1; k <= Topo::J; ++k) io.rot_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
+    return launch_evaluate_build(ch, io.e.n, [&](auto t, dim3 grid, dim3 threads) {
+        hipLaunchKernelGGL((k_evaluate_frames<Topo, MODE, decltype(t)::value>), grid, threads, 0, stream, cc, io);
+    });
 }
 
 }  // namespace ikpso

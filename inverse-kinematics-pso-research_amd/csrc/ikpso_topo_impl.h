@@ -1,5 +1,5 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, PoseOps<Topo>, AimOps<Topo>,
-// FramesOps<Topo> and EvalFramesOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo> and
+// EvalFramesOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
@@ -21,22 +21,10 @@ hipError_t TrackOps<Topo, MODE>::resident(const ChainHost& ch, const SwarmIO& io
     return run_resident<Topo, MODE, true>(ch, io, block, s);
 }
 
-template <class Topo>
-hipError_t PoseOps<Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
+template <int TERM, class Topo>
+hipError_t TermTrackOps<TERM, Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
 {
-    return run_resident_pose<Topo>(ch, io, block, s);
-}
-
-template <class Topo>
-hipError_t AimOps<Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
-{
-    return run_resident_aim<Topo>(ch, io, block, s);
-}
-
-template <class Topo>
-hipError_t FramesOps<Topo>::track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t s)
-{
-    return run_resident_frames<Topo>(ch, io, block, s);
+    return run_resident_term<Topo, TERM>(ch, io, block, s);
 }
 
 template <class Topo, int MODE>

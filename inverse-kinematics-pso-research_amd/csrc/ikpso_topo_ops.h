@@ -8,6 +8,7 @@
 
 #include <type_traits>
 
+#include "ikpso_device.h"
 #include "ikpso_kernels.h"
 
 namespace ikpso {
@@ -27,23 +28,12 @@ struct TrackOps {
     static hipError_t resident(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
-// The folded chain's pose track kernels (ikpso_solve_track_pose; TopoDH only, FAST), in units of
-// their own again (ikpso_inst_pose_dh_*.hip).
-template <class Topo>
-struct PoseOps {
-    static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
-};
-
-// The folded chain's aim track kernels (ikpso_solve_track_aim), likewise (ikpso_inst_aim_dh_*.hip).
-template <class Topo>
-struct AimOps {
-    static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
-};
-
-// The Euler topologies' effector-frame track kernels (ikpso_solve_track_frames; FAST, every topology but
-// TopoDH), likewise (ikpso_inst_frames_*.hip).
-template <class Topo>
-struct FramesOps {
+// The track kernels with a term of their own (FAST only), in units of their own again:
+//   TermTrackOps<kTermOrient, TopoDH<J>>    ikpso_solve_track_pose    ikpso_inst_pose_dh_*.hip
+//   TermTrackOps<kTermAim, TopoDH<J>>       ikpso_solve_track_aim     ikpso_inst_aim_dh_*.hip
+//   TermTrackOps<kTermOrient, Euler Topo>   ikpso_solve_track_frames  ikpso_inst_frames_*.hip
+template <int TERM, class Topo>
+struct TermTrackOps {
     static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
@@ -77,26 +67,15 @@ struct TopoOps {
     {
         return with_mode(mode, [&](auto m) { return TrackOps<Topo, decltype(m)::value>::resident(ch, io, block, s); });
     }
-    static hipError_t pose_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
+    // TERM's track kernels: the folded chain has the tip's orientation and aim terms, the Euler topologies
+    // the orientation term per effector; no other kernel has either
+    template <int TERM>
+    static hipError_t term_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
     {
-        if constexpr (Topo::kDH) {
-            if (mode == IKPSO_ARITH_FAST) return PoseOps<Topo>::track(ch, io, block, s);
+        if constexpr (TERM == kTermOrient || (TERM == kTermAim && Topo::kDH)) {
+            if (mode == IKPSO_ARITH_FAST) return TermTrackOps<TERM, Topo>::track(ch, io, block, s);
         }
-        return hipErrorNotSupported;  // no other kernel has the orientation term
-    }
-    static hipError_t aim_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
-    {
-        if constexpr (Topo::kDH) {
-            if (mode == IKPSO_ARITH_FAST) return AimOps<Topo>::track(ch, io, block, s);
-        }
-        return hipErrorNotSupported;  // no other kernel has the aim term
-    }
-    static hipError_t frames_track(const ChainHost& ch, int mode, const SwarmIO& io, int block, hipStream_t s)
-    {
-        if constexpr (!Topo::kDH) {
-            if (mode == IKPSO_ARITH_FAST) return FramesOps<Topo>::track(ch, io, block, s);
-        }
-        return hipErrorNotSupported;  // no other kernel has the effector rotation term
+        return hipErrorNotSupported;
     }
     static hipError_t stream(const ChainHost& ch, int mode, const StreamIO& io, int iterations, hipStream_t s)
     {

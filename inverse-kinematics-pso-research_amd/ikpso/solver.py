@@ -219,6 +219,7 @@ class BatchSolver:
         self.dof = self._lib.ikpso_solver_dof(self._h)
         self.effectors = self._lib.ikpso_solver_effectors(self._h)
         self.capacity = 0
+        self._seeded_on = None
 
     @property
     def collider_count(self) -> int:
@@ -234,7 +235,7 @@ class BatchSolver:
         torch = _torch()
         _abi.check(self._lib.ikpso_solver_seed(self._h, int(capacity), int(seed_base), int(first_swarm),
                                                _stream_handle(stream)), "ikpso_solver_seed")
-        self._device = torch.device("cuda", torch.cuda.current_device())  # where the generator states live
+        self._seeded_on = torch.device("cuda", torch.cuda.current_device())  # where the generator states live
         self.capacity = max(self.capacity, int(capacity))
 
     def _check_tensor(self, t, name: str, device) -> None:
@@ -268,7 +269,7 @@ class BatchSolver:
             raise ValueError(f"targets must be [{B}, {self.effectors}, 3]")
         if start_pose is not None and tuple(start_pose.shape) != (B, self.dof):
             raise ValueError(f"start_pose must be [{B}, {self.dof}]")
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+        dev = self._device()
         if out is None:
             angles = torch.empty((B, self.dof), dtype=torch.float32, device=dev)
             fitness = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -288,70 +289,81 @@ class BatchSolver:
             _abi.check(self._lib.ikpso_solver_sync(self._h), "ikpso_solver_sync")
         return angles, fitness, res
 
-    def _solve_pose(self, targets, target_rot, orientation_weight: float, start_pose, B: int, T: int, it: int,
-                    stop: float, outs, stream) -> None:
-        """ikpso_solve_track_pose over time-major buffers: target_rot holds T * B row-major 3x3
-        rotations of the effector node's frame."""
+    def _device(self):
+        """Where the generator states live (seed()); before any, the current device."""
         torch = _torch()
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
-        if target_rot.numel() != T * B * 9 or tuple(target_rot.shape[-2:]) != (3, 3):
-            raise ValueError(f"target_rot must hold {T * B} rotations [..., 3, 3]")
-        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (target_rot, "target_rot")):
-            self._check_tensor(t, name, dev)
-        angles, fitness, res, iters = outs
-        _abi.check(self._lib.ikpso_solve_track_pose(self._h, _dev_ptr(targets), _dev_ptr(target_rot),
-                                                    float(orientation_weight), _dev_ptr(start_pose), B, T, it, stop,
-                                                    _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
-                                                    _dev_ptr(iters), _stream_handle(stream)),
-                   "ikpso_solve_track_pose")
+        return self._seeded_on or torch.device("cuda", torch.cuda.current_device())
 
-    def _solve_aim(self, targets, aim_dir, aim_axis, aim_weight: float, start_pose, B: int, T: int, it: int,
-                   stop: float, outs, stream) -> None:
-        """ikpso_solve_track_aim over time-major buffers: aim_dir holds T * B world directions, aim_axis
-        (host, 3 values) the tool axis in the effector node's frame."""
+    def _outputs(self, shape: Tuple[int, ...], residual: bool, dev):
+        """(angles [*shape, D], fitness [*shape], residual [*shape] or None, iterations [*shape] int32)"""
         torch = _torch()
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
-        if aim_dir.numel() != T * B * 3 or int(aim_dir.shape[-1]) != 3:
-            raise ValueError(f"aim_dir must hold {T * B} directions [..., 3]")
-        axis = np.asarray(aim_axis, dtype=np.float32).reshape(-1)
-        if axis.shape != (3,):
-            raise ValueError("aim_axis must hold 3 values")
-        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (aim_dir, "aim_dir")):
-            self._check_tensor(t, name, dev)
-        angles, fitness, res, iters = outs
-        host_axis = (ctypes.c_float * 3)(*axis.tolist())  # read during the call
-        _abi.check(self._lib.ikpso_solve_track_aim(self._h, _dev_ptr(targets), _dev_ptr(aim_dir), host_axis,
-                                                   float(aim_weight), _dev_ptr(start_pose), B, T, it, stop,
-                                                   _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
-                                                   _dev_ptr(iters), _stream_handle(stream)),
-                   "ikpso_solve_track_aim")
+        return (torch.empty(shape + (self.dof,), dtype=torch.float32, device=dev),
+                torch.empty(shape, dtype=torch.float32, device=dev),
+                torch.empty(shape, dtype=torch.float32, device=dev) if residual else None,
+                torch.empty(shape, dtype=torch.int32, device=dev))
 
-    def _solve_frames(self, targets, effector_rot, effector_rot_weight, start_pose, B: int, T: int, it: int,
-                      stop: float, outs, stream) -> None:
-        """ikpso_solve_track_frames over time-major buffers: effector_rot holds T * B * E row-major 3x3
-        rotations (or is None with every weight 0), effector_rot_weight one weight or E of them (host)."""
-        torch = _torch()
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
+    def _host_weights(self, effector_rot_weight):
+        """effector_rot_weight (a scalar or E values) as the E host floats an entry reads during the call;
+        None (every weight 0) stays None."""
+        if effector_rot_weight is None:
+            return None
         E = self.effectors
-        if effector_rot is not None and (effector_rot.numel() != T * B * E * 9 or
-                                         tuple(effector_rot.shape[-2:]) != (3, 3)):
-            raise ValueError(f"effector_rot must hold {T * B * E} rotations [..., {E}, 3, 3]")
-        host_w = None  # no weights: every weight 0
-        if effector_rot_weight is not None:
-            w = np.asarray(effector_rot_weight, dtype=np.float32).reshape(-1)
-            if w.size == 1:
-                w = np.repeat(w, E)
-            if w.shape != (E,):
-                raise ValueError(f"effector_rot_weight must be a scalar or hold {E} values")
-            host_w = (ctypes.c_float * E)(*w.tolist())  # read during the call
-        for t, name in ((targets, "targets"), (start_pose, "start_pose"), (effector_rot, "effector_rot")):
-            self._check_tensor(t, name, dev)
-        angles, fitness, res, iters = outs
-        _abi.check(self._lib.ikpso_solve_track_frames(self._h, _dev_ptr(targets), _dev_ptr(effector_rot), host_w,
-                                                      _dev_ptr(start_pose), B, T, it, stop, _dev_ptr(angles),
-                                                      _dev_ptr(fitness), _dev_ptr(res), _dev_ptr(iters),
-                                                      _stream_handle(stream)),
-                   "ikpso_solve_track_frames")
+        w = np.asarray(effector_rot_weight, dtype=np.float32).reshape(-1)
+        if w.size == 1:
+            w = np.repeat(w, E)
+        if w.shape != (E,):
+            raise ValueError(f"effector_rot_weight must be a scalar or hold {E} values")
+        return (ctypes.c_float * E)(*w.tolist())
+
+    @staticmethod
+    def _term_form(target_rot, orientation_weight, aim_dir, aim_axis, aim_weight, effector_rot, effector_rot_weight):
+        """The form the term arguments of solve_until / solve_track select, as (name, the form's device
+        tensor, its host arguments); (None, None, None) for the plain call."""
+        if target_rot is not None and aim_dir is not None:
+            raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
+        frames_form = effector_rot is not None or effector_rot_weight is not None
+        if frames_form and (target_rot is not None or aim_dir is not None):
+            raise ValueError("effector_rot is not combined with target_rot or aim_dir: pass one or the other")
+        if target_rot is not None:
+            return "pose", target_rot, orientation_weight
+        if aim_dir is not None:
+            return "aim", aim_dir, (aim_axis, aim_weight)
+        if frames_form:
+            return "effector_rot", effector_rot, effector_rot_weight
+        return None, None, None
+
+    def _solve_form(self, form, targets, start_pose, B: int, T: int, it: int, stop: float, outs, stream) -> None:
+        """ikpso_solve_track, or the entry of `form` (_term_form), over time-major buffers.  "pose": T * B
+        row-major 3x3 rotations of the effector node's frame, and the weight.  "aim": T * B world
+        directions, and (the tool axis in the effector node's frame, 3 host values; the weight).
+        "effector_rot": T * B * E row-major 3x3 rotations (or None with every weight 0), and one weight or
+        E of them (host)."""
+        name, extra, host = form
+        E = self.effectors
+        if name == "pose":
+            if extra.numel() != T * B * 9 or tuple(extra.shape[-2:]) != (3, 3):
+                raise ValueError(f"target_rot must hold {T * B} rotations [..., 3, 3]")
+            entry, tensor, term = "ikpso_solve_track_pose", "target_rot", lambda p: (p, float(host))
+        elif name == "aim":
+            if extra.numel() != T * B * 3 or int(extra.shape[-1]) != 3:
+                raise ValueError(f"aim_dir must hold {T * B} directions [..., 3]")
+            axis = np.asarray(host[0], dtype=np.float32).reshape(-1)
+            if axis.shape != (3,):
+                raise ValueError("aim_axis must hold 3 values")
+            host_axis = (ctypes.c_float * 3)(*axis.tolist())  # read during the call
+            entry, tensor, term = "ikpso_solve_track_aim", "aim_dir", lambda p: (p, host_axis, float(host[1]))
+        elif name == "effector_rot":
+            if extra is not None and (extra.numel() != T * B * E * 9 or tuple(extra.shape[-2:]) != (3, 3)):
+                raise ValueError(f"effector_rot must hold {T * B * E} rotations [..., {E}, 3, 3]")
+            host_w = self._host_weights(host)
+            entry, tensor, term = "ikpso_solve_track_frames", "effector_rot", lambda p: (p, host_w)
+        else:
+            entry, tensor, term = "ikpso_solve_track", "", lambda p: ()
+        for t, tname in ((targets, "targets"), (start_pose, "start_pose"), (extra, tensor)):
+            self._check_tensor(t, tname, self._device())
+        _abi.check(getattr(self._lib, entry)(self._h, _dev_ptr(targets), *term(_dev_ptr(extra)), _dev_ptr(start_pose),
+                                             B, T, it, stop, *(_dev_ptr(o) for o in outs), _stream_handle(stream)),
+                   entry)
 
     def solve_until(self, targets=None, start_pose=None, max_iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, num_swarms: Optional[int] = None, residual: bool = True,
@@ -370,12 +382,8 @@ class BatchSolver:
         and aim_weight: the aim form, likewise; not together with target_rot.  effector_rot (device
         [B, E, 3, 3] float32) with effector_rot_weight: per-effector orientation targets of an unmasked
         Euler chain or tree, one frame of solve_track's; not together with either."""
-        torch = _torch()
-        if target_rot is not None and aim_dir is not None:
-            raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
-        frames_form = effector_rot is not None or effector_rot_weight is not None
-        if frames_form and (target_rot is not None or aim_dir is not None):
-            raise ValueError("effector_rot is not combined with target_rot or aim_dir: pass one or the other")
+        form = self._term_form(target_rot, orientation_weight, aim_dir, aim_axis, aim_weight, effector_rot,
+                               effector_rot_weight)
         if num_swarms is None:
             if targets is None:
                 raise ValueError("num_swarms is required when targets is None")
@@ -387,36 +395,20 @@ class BatchSolver:
             raise ValueError(f"targets must be [{B}, {self.effectors}, 3]")
         if start_pose is not None and tuple(start_pose.shape) != (B, self.dof):
             raise ValueError(f"start_pose must be [{B}, {self.dof}]")
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
-        angles = torch.empty((B, self.dof), dtype=torch.float32, device=dev)
-        fitness = torch.empty((B,), dtype=torch.float32, device=dev)
-        res = torch.empty((B,), dtype=torch.float32, device=dev) if residual else None
-        iters = torch.empty((B,), dtype=torch.int32, device=dev)
-        if target_rot is not None:
+        dev = self._device()
+        outs = angles, fitness, res, iters = self._outputs((B,), residual, dev)
+        if form[0] is not None:
             if targets is None:
-                raise ValueError("the pose form needs targets")
-            self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, 1, it, stop,
-                             (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
-        if aim_dir is not None:
-            if targets is None:
-                raise ValueError("the aim form needs targets")
-            self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, 1, it, stop,
-                            (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
-        if frames_form:
-            if targets is None:
-                raise ValueError("the effector_rot form needs targets")
-            self._solve_frames(targets, effector_rot, effector_rot_weight,
-                               start_pose, B, 1, it, stop, (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
+                raise ValueError(f"the {form[0]} form needs targets")
+            self._solve_form(form, targets, start_pose, B, 1, it, stop, outs, stream)
+            return outs
         for t, name in ((targets, "targets"), (start_pose, "start_pose")):
             self._check_tensor(t, name, dev)
         _abi.check(self._lib.ikpso_solve_batch_until(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, it, stop,
                                                      _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res),
                                                      _dev_ptr(iters), _stream_handle(stream)),
                    "ikpso_solve_batch_until")
-        return angles, fitness, res, iters
+        return outs
 
     def solve_track(self, targets, start_pose=None, iterations: Optional[int] = None,
                     stop_fitness: Optional[float] = None, residual: bool = True, stream=None, target_rot=None,
@@ -456,12 +448,8 @@ class BatchSolver:
         family; every other solver raises (unsupported configuration).  With every weight 0 (or
         effector_rot_weight=None) the answers equal the call without the term, bit for bit.  Not
         combined with target_rot or aim_dir (ValueError)."""
-        torch = _torch()
-        if target_rot is not None and aim_dir is not None:
-            raise ValueError("target_rot and aim_dir are not combined: pass one or the other")
-        frames_form = effector_rot is not None or effector_rot_weight is not None
-        if frames_form and (target_rot is not None or aim_dir is not None):
-            raise ValueError("effector_rot is not combined with target_rot or aim_dir: pass one or the other")
+        form = self._term_form(target_rot, orientation_weight, aim_dir, aim_axis, aim_weight, effector_rot,
+                               effector_rot_weight)
         if targets is None or targets.dim() != 4:
             raise ValueError(f"targets must be [T, B, {self.effectors}, 3]")
         T, B = int(targets.shape[0]), int(targets.shape[1])
@@ -471,29 +459,9 @@ class BatchSolver:
             raise ValueError(f"targets must be [{T}, {B}, {self.effectors}, 3]")
         if start_pose is not None and tuple(start_pose.shape) != (B, self.dof):
             raise ValueError(f"start_pose must be [{B}, {self.dof}]")
-        dev = getattr(self, "_device", None) or torch.device("cuda", torch.cuda.current_device())
-        angles = torch.empty((T, B, self.dof), dtype=torch.float32, device=dev)
-        fitness = torch.empty((T, B), dtype=torch.float32, device=dev)
-        res = torch.empty((T, B), dtype=torch.float32, device=dev) if residual else None
-        iters = torch.empty((T, B), dtype=torch.int32, device=dev)
-        if target_rot is not None:
-            self._solve_pose(targets, target_rot, orientation_weight, start_pose, B, T, it, stop,
-                             (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
-        if aim_dir is not None:
-            self._solve_aim(targets, aim_dir, aim_axis, aim_weight, start_pose, B, T, it, stop,
-                            (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
-        if frames_form:
-            self._solve_frames(targets, effector_rot, effector_rot_weight,
-                               start_pose, B, T, it, stop, (angles, fitness, res, iters), stream)
-            return angles, fitness, res, iters
-        for t, name in ((targets, "targets"), (start_pose, "start_pose")):
-            self._check_tensor(t, name, dev)
-        _abi.check(self._lib.ikpso_solve_track(self._h, _dev_ptr(targets), _dev_ptr(start_pose), B, T, it, stop,
-                                               _dev_ptr(angles), _dev_ptr(fitness), _dev_ptr(res), _dev_ptr(iters),
-                                               _stream_handle(stream)), "ikpso_solve_track")
-        return angles, fitness, res, iters
+        outs = self._outputs((T, B), residual, self._device())
+        self._solve_form(form, targets, start_pose, B, T, it, stop, outs, stream)
+        return outs
 
     def sync(self) -> None:
         """ikpso_solver_sync: settle the last solve (see solve(sync=...))."""
@@ -551,14 +519,7 @@ class BatchSolver:
             raise ValueError(f"rest must be [{n}, {self.dof}]")
         if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
             raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
-        host_w = None  # no weights: every weight 0
-        if effector_rot_weight is not None:
-            w = np.asarray(effector_rot_weight, dtype=np.float32).reshape(-1)
-            if w.size == 1:
-                w = np.repeat(w, E)
-            if w.shape != (E,):
-                raise ValueError(f"effector_rot_weight must be a scalar or hold {E} values")
-            host_w = (ctypes.c_float * E)(*w.tolist())  # read during the call
+        host_w = self._host_weights(effector_rot_weight)
         for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
             self._check_tensor(t, name, angles.device)
         fit = torch.empty((n,), dtype=torch.float32, device=angles.device)
