@@ -487,6 +487,52 @@ ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* solver, const float* ang
                                           int64_t n, float* out_fitness, float* out_positions,
                                           float* out_rotations, float* out_rot_error, void* stream);
 
+/* The geometric Jacobian of every effector at given angle vectors, on the device (added
+ * after ABI 5; detect by symbol): how the positions and rotations the evaluate entries
+ * report change with the joint angles -- for a Gauss-Newton polish of an answer, velocity
+ * IK between the frames of a track, manipulability and singularity checks.
+ *   angles         exactly ikpso_solver_evaluate's: device, [n][D], the free dimensions
+ *                  under an axis mask, locked axes at the chain's rotation, always the
+ *                  Euler form of the chain.
+ *   out_positions  device, [n][J][3] or NULL: ikpso_solver_evaluate's output, with the
+ *                  caveat ikpso_solver_evaluate_frames states (in REFERENCE arithmetic
+ *                  the same values; in FAST the rounding any two FAST builds differ by).
+ *   out_jacobian   device, [n][E][6][D], required when n > 0.  Effectors in node order,
+ *                  as targets indexes them; rows 0..2 the linear part, rows 3..5 the
+ *                  angular part, both in world coordinates; columns the D free
+ *                  dimensions in the solver's own order (node order, then axis order
+ *                  within a node).
+ * No targets, rest pose or weights: the Jacobian depends on none of them.
+ * Definition, with the frames as ikpso_solve_track_pose defines them: node k's frame is
+ * frame(parent(k)) Rx(x_k) Ry(y_k) Rz(z_k) T(length_k, 0, 0), frame(0) the origin's
+ * position and fixed Rx Ry Rz; R_k is its rotation, p_k its position (p_0 the origin's).
+ * For effector e at node m and free dimension d, the angle c of node k:
+ *   k is m or an ancestor of m: the column is (a x (p_m - p_parent(k)), a), a the world
+ *     axis of that angle,
+ *       c = 0 (x): a = R_parent(k) e_x
+ *       c = 1 (y): a = R_parent(k) Rx(x_k) e_y
+ *       c = 2 (z): a = R_k e_z
+ *     The angular part means dR_m / d theta_d = [a]x R_m.
+ *   otherwise: all six entries are exactly +0.0f (the other wrists of the 7-node scene,
+ *     the other fingers of a tree).
+ * A DH arm is evaluated through its masked Euler chain, as ikpso_solver_evaluate does: its
+ * D columns are the arm's joints, and the constant tool rotation between the effector
+ * node's frame and the DH tool frame does not change the world angular velocity, so the
+ * rows need no conversion.
+ * FAST kernels on the hardware sin/cos take the axes from the rotation
+ * ikpso_solver_evaluate_frames returns (that unit's known amplitude bias added back), so
+ * |a| = 1 to float32 rounding; the positions are untouched, as in that entry.
+ * Served is every solver ikpso_solver_evaluate serves -- FAST and REFERENCE, masked
+ * chains, folded DH arms, trees, chains with colliders, every compiled topology -- routed
+ * as evaluate routes it.  A collider changes nothing in the output; only the build's
+ * arithmetic follows it.  Nothing evaluate accepts is refused.
+ * IKPSO_ERR_INVALID_ARG: a NULL solver; n < 0; n > 0 with a NULL angles or a NULL
+ * out_jacobian.  n == 0 is IKPSO_OK with no device work.  Stream-ordered: the call does
+ * not synchronise, and like ikpso_solver_evaluate it neither waits for nor settles a
+ * pending solve. */
+ikpso_status ikpso_solver_evaluate_jacobian(ikpso_solver* solver, const float* angles, int64_t n,
+                                            float* out_positions, float* out_jacobian, void* stream);
+
 /* Copy the generator states of local swarms [first_swarm, first_swarm + count)
  * (P states each, swarm-major, 48-byte curandState layout) into dst (any memory,
  * count * P states), after settling a pending solve (ABI >= 5).  Synchronises

@@ -1147,6 +1147,21 @@ ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* s, const float* angles, 
     return IKPSO_OK;
 }
 
+// ikpso_solver_evaluate's angle vectors on the Jacobian kernels: every solver evaluate serves, no targets,
+// rest pose or weights (the Jacobian depends on none of them).
+ikpso_status ikpso_solver_evaluate_jacobian(ikpso_solver* s, const float* angles, int64_t n, float* out_positions,
+                                            float* out_jacobian, void* stream)
+{
+    if (!s || n < 0 || (n > 0 && (!angles || !out_jacobian))) return IKPSO_ERR_INVALID_ARG;
+    JacobianIO io{};
+    io.angles = angles;
+    io.out_positions = out_positions;
+    io.out_jacobian = out_jacobian;
+    io.n = n;
+    IKPSO_HIP(launch_evaluate_jacobian(s->chain, s->mode, io, (hipStream_t)stream));
+    return IKPSO_OK;
+}
+
 int ikpso_solver_dof(const ikpso_solver* s) { return s ? s->chain.dof() : 0; }
 int ikpso_solver_effectors(const ikpso_solver* s) { return s ? s->chain.E : 0; }
 int ikpso_solver_collider_count(const ikpso_solver* s) { return s ? s->chain.num_coll : 0; }

@@ -168,4 +168,19 @@ struct StreamIO {
     int32_t* out_iterations;    // [B] or null: written by the finalize launch
 };
 
+// Parameters of the Jacobian kernel (ikpso_solver_evaluate_jacobian): the evaluate kernel's angle vectors
+// in, the node positions and the geometric Jacobian of every effector out.
+struct JacobianIO {
+    const float* angles;   // [n][dfree]
+    float* out_positions;  // [n][J][3] or null
+    float* out_jacobian;   // [n][E][6][dfree]: rows 0..2 linear, 3..5 angular, world coordinates
+    int64_t n;
+    // The builds on the transcendental unit's sin/cos scale the joint axes back to unit length
+    // (run_evaluate_jacobian fills both, at k - 1): frame_comp is EvalFramesIO::rot_comp, 2 depth(k) eps, for
+    // the axes that are columns of a node's frame; axis_y_comp is (2 depth(k) - 1) eps, for node k's y axis,
+    // a column of the parent's frame turned by the node's Rx alone.
+    float frame_comp[kMaxEffFrames];
+    float axis_y_comp[kMaxEffFrames];
+};
+
 }  // namespace ikpso

@@ -1,8 +1,9 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo> and
-// EvalFramesOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo>,
+// EvalFramesOps<Topo, MODE> and JacobianOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
+#include "ikpso_jacobian.h"
 #include "ikpso_resident.h"
 #include "ikpso_stream.h"
 #include "ikpso_topo_ops.h"
@@ -43,6 +44,12 @@ template <class Topo, int MODE>
 hipError_t EvalFramesOps<Topo, MODE>::evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t s)
 {
     return run_evaluate_frames<Topo, MODE>(ch, io, s);
+}
+
+template <class Topo, int MODE>
+hipError_t JacobianOps<Topo, MODE>::evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t s)
+{
+    return run_evaluate_jacobian<Topo, MODE>(ch, io, s);
 }
 
 template <class Topo, int MODE>

@@ -44,6 +44,13 @@ struct EvalFramesOps {
     static hipError_t evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t stream);
 };
 
+// The Jacobian kernels (ikpso_solver_evaluate_jacobian; every Euler topology, both modes), likewise
+// (ikpso_inst_jacobian_*.hip).
+template <class Topo, int MODE>
+struct JacobianOps {
+    static hipError_t evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -91,6 +98,13 @@ struct TopoOps {
             return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
         else
             return with_mode(mode, [&](auto m) { return EvalFramesOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
+    }
+    static hipError_t evaluate_jacobian(const ChainHost& ch, int mode, const JacobianIO& io, hipStream_t s)
+    {
+        if constexpr (Topo::kDH)
+            return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
+        else
+            return with_mode(mode, [&](auto m) { return JacobianOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
     static hipError_t coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t s)
     {

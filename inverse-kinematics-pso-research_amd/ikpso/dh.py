@@ -108,7 +108,10 @@ class DHArm:
     (marshal it with origin.to_cuda()); `joint_nodes[i]` carries theta_i in its
     z angle, offset by `z_offset[i]`; `tool` is the effector node.  `tool_rotation` is the
     constant K with (DH tool frame) = (effector node frame) K: Rx(alpha_n), preceded by Ry(-beta)
-    when the last joint has d != 0 (the fixed rotation a further joint would have carried in)."""
+    when the last joint has d != 0 (the fixed rotation a further joint would have carried in).
+    BatchSolver.jacobian needs no such conversion: its D columns are the arm's joints, and a constant
+    rotation on the right of the node frame does not change the world angular velocity
+    (d(R K)/dt (R K)^T = dR/dt R^T), so the node's angular rows are the DH tool frame's."""
 
     origin: OriginNode
     joint_nodes: List[Node]

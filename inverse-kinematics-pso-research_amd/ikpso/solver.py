@@ -123,6 +123,15 @@ def rotation_angle(rot_error):
     return np.arccos(np.clip(1.0 - np.asarray(rot_error) / 4.0, -1.0, 1.0))
 
 
+def manipulability(jac, rows=slice(0, 3)) -> np.ndarray:
+    """Yoshikawa's manipulability sqrt(det(J J^T)) over the chosen rows of BatchSolver.jacobian's [..., 6, D]
+    Jacobians (rows 0..2 linear, the default; 3..5 angular; slice(0, 6) both), in numpy float64: [...].  0 at a
+    singularity of those rows, and wherever D is smaller than their number."""
+    j = jac.detach().cpu().numpy() if hasattr(jac, "detach") else np.asarray(jac)
+    j = j.astype(np.float64)[..., rows, :]
+    return np.sqrt(np.maximum(np.linalg.det(j @ np.swapaxes(j, -1, -2)), 0.0))
+
+
 def rng_tensor(count: int, device="cuda"):
     """Device buffer for `count` generator states (48 bytes each, curandState_t layout)."""
     torch = _torch()
@@ -532,6 +541,26 @@ class BatchSolver:
                                                           _stream_handle(stream)),
                    "ikpso_solver_evaluate_frames")
         return fit, pos, rot, err
+
+    def jacobian(self, angles, stream=None):
+        """The geometric Jacobian of every effector at given angle vectors (ikpso_solver_evaluate_jacobian):
+        (jac [n, E, 6, D], node positions [n, J, 3]).  angles [n, D] is evaluate()'s.  jac[i, e] has rows 0..2
+        d(position of effector e)/d(angle) and rows 3..5 the angular part, both in world coordinates, one
+        column per free dimension in the solver's order (node order, then axis order); effectors in node
+        order as in targets; a dimension off the effector's path to the root has a column of zeros.
+        manipulability() takes the result.  Every solver evaluate() serves is served."""
+        torch = _torch()
+        n = int(angles.shape[0])
+        E, J = self.effectors, self.chain.shape[0] - 1
+        if tuple(angles.shape) != (n, self.dof):
+            raise ValueError(f"angles must be [n, {self.dof}]")
+        self._check_tensor(angles, "angles", angles.device)
+        jac = torch.empty((n, E, 6, self.dof), dtype=torch.float32, device=angles.device)
+        pos = torch.empty((n, J, 3), dtype=torch.float32, device=angles.device)
+        _abi.check(self._lib.ikpso_solver_evaluate_jacobian(self._h, _dev_ptr(angles), n, _dev_ptr(pos), _dev_ptr(jac),
+                                                            _stream_handle(stream)),
+                   "ikpso_solver_evaluate_jacobian")
+        return jac, pos
 
     def close(self) -> None:
         if getattr(self, "_h", None):
