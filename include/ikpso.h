@@ -533,6 +533,65 @@ ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* solver, const float* ang
 ikpso_status ikpso_solver_evaluate_jacobian(ikpso_solver* solver, const float* angles, int64_t n,
                                             float* out_positions, float* out_jacobian, void* stream);
 
+/* The fitness ikpso_solver_evaluate_frames reports and its gradient with respect to the joint
+ * angles, on the device (added after ABI 5; detect by symbol): what a first-order or
+ * quasi-Newton optimiser (L-BFGS-B with the joint bounds, projected gradient descent) needs to
+ * polish a batch of PSO answers against the solver's own objective -- every term of it, the
+ * distance term, the angle term and the soft-limit penalty included, which the effector
+ * Jacobians alone do not cover.
+ *   angles, targets, rest, target_rot, rot_weights (host memory, E floats), n
+ *                  exactly ikpso_solver_evaluate_frames': the free dimensions under an axis
+ *                  mask, locked axes at the chain's rotation, NULL targets the chain's own,
+ *                  always the Euler form of the chain.
+ *   out_fitness    device, [n] or NULL: the fitness ikpso_solver_evaluate_frames reports for
+ *                  the same arguments, a collider's FLT_MAX included.
+ *   out_gradient   device, [n][D], required when n > 0: column d is the derivative of that
+ *                  fitness with respect to free dimension d, in the solver's own order (node
+ *                  order, then axis order within a node).
+ * Definition, with the frames R_k, p_k and the world axes a of
+ * ikpso_solver_evaluate_jacobian.  For free dimension d, the angle c of node k, with
+ * q = p_parent(k) the angle's pivot and S(k) node k and its descendants, the gradient is the
+ * sum of
+ *   effector positions   sum over the effectors m in S(k) of
+ *                          2 eff_w[m] (p_m - t_m) . (a x (p_m - q))
+ *   distance term        (distance_weight != 0 only) sum over every node m in S(k) of
+ *                          2 dw (p_m - ref_m) . (a x (p_m - q)),
+ *                        dw = distance_weight / J and ref_m the slot of the positions array
+ *                        the fitness reads (IKPSO_FLAG_POSREF_NODE_SLOT or the reference's);
+ *                        the constant (1 - ref_w)^2 of that term contributes nothing
+ *   angle term           2 aw (x_d - rest_d), aw = angle_weight / J
+ *   soft-limit penalty   2 limit_weight (x_d - soft_hi[d]) above the soft bound,
+ *                        -2 limit_weight (soft_lo[d] - x_d) below it, 0 between and at the
+ *                        bounds: the penalty is C1, so the gradient is continuous
+ *   rotation term        sum over the effectors m in S(k), effector e, rot_weights[e] != 0, of
+ *                          2 eff_w[m] rot_weights[e] a . v(R_m T_e^T),
+ *                        v(M) = (M32 - M23, M13 - M31, M21 - M12): from
+ *                        |R - T|_F^2 = |R|^2 - 2 tr(T^T R) + |T|^2 and dR / d theta = [a]x R;
+ *                        T is used as given, orthonormal or not, and an effector of weight 0
+ *                        never has its target read.
+ * The angle term and the penalty are rounded as written, one product each and their sum, in
+ * both arithmetics: a dimension with no effector (and, with the distance term, no node) below
+ * it returns exactly that value.
+ * Colliders: a fitness the collider term set to FLT_MAX stays FLT_MAX in out_fitness, and
+ * out_gradient is always the gradient of the smooth terms above -- finite, and the same
+ * whether or not the pose collides.  A caller polishing answers tests out_fitness.
+ * The pose and aim terms of the folded kernels have no entry in
+ * ikpso_solver_evaluate_frames and none here; for E = 1 the rotation term is
+ * ikpso_solve_track_pose's with orientation_weight = rot_weights[0], as that entry documents.
+ * FAST kernels on the hardware sin/cos scale the axes and the rotation R_m as
+ * ikpso_solver_evaluate_jacobian and ikpso_solver_evaluate_frames do.
+ * Served is every solver ikpso_solver_evaluate serves -- FAST and REFERENCE, masked chains,
+ * folded DH arms through their Euler chain, trees, chains with colliders, every compiled
+ * topology -- routed as evaluate routes it.  Nothing evaluate accepts is refused.
+ * IKPSO_ERR_INVALID_ARG: what ikpso_solver_evaluate_frames rejects (a NULL solver; n < 0;
+ * n > 0 with a NULL angles; a NaN, infinite or negative weight; some weight > 0 with a NULL
+ * target_rot), and n > 0 with a NULL out_gradient.  n == 0 is IKPSO_OK with no device work.
+ * Stream-ordered: the call does not synchronise, and it neither waits for nor settles a
+ * pending solve. */
+ikpso_status ikpso_solver_evaluate_gradient(ikpso_solver* solver, const float* angles, const float* targets,
+                                            const float* rest, const float* target_rot, const float* rot_weights,
+                                            int64_t n, float* out_fitness, float* out_gradient, void* stream);
+
 /* Copy the generator states of local swarms [first_swarm, first_swarm + count)
  * (P states each, swarm-major, 48-byte curandState layout) into dst (any memory,
  * count * P states), after settling a pending solve (ABI >= 5).  Synchronises

@@ -1162,6 +1162,28 @@ ikpso_status ikpso_solver_evaluate_jacobian(ikpso_solver* s, const float* angles
     return IKPSO_OK;
 }
 
+// ikpso_solver_evaluate_frames' inputs on the gradient kernels: every solver evaluate serves; the fitness of
+// that entry and its derivative with respect to every free angle.
+ikpso_status ikpso_solver_evaluate_gradient(ikpso_solver* s, const float* angles, const float* targets,
+                                            const float* rest, const float* target_rot, const float* rot_weights,
+                                            int64_t n, float* out_fitness, float* out_gradient, void* stream)
+{
+    if (!s || n < 0 || (n > 0 && (!angles || !out_gradient))) return IKPSO_ERR_INVALID_ARG;
+    GradientIO io{};
+    bool weighted = false;
+    if (!effector_weights(rot_weights, s->chain.E, io.rot_w, &weighted)) return IKPSO_ERR_INVALID_ARG;
+    if (weighted && !target_rot) return IKPSO_ERR_INVALID_ARG;
+    io.angles = angles;
+    io.targets = targets;
+    io.rest = rest;
+    io.target_rot = target_rot;
+    io.out_fitness = out_fitness;
+    io.out_gradient = out_gradient;
+    io.n = n;
+    IKPSO_HIP(launch_evaluate_gradient(s->chain, s->mode, io, (hipStream_t)stream));
+    return IKPSO_OK;
+}
+
 int ikpso_solver_dof(const ikpso_solver* s) { return s ? s->chain.dof() : 0; }
 int ikpso_solver_effectors(const ikpso_solver* s) { return s ? s->chain.E : 0; }
 int ikpso_solver_collider_count(const ikpso_solver* s) { return s ? s->chain.num_coll : 0; }

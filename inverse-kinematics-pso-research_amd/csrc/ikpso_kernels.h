@@ -281,6 +281,7 @@ size_t stream_workspace_bytes(int64_t B, int P, int D, bool with_state);
 hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipStream_t stream);
 hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream);
 hipError_t launch_evaluate_jacobian(const ChainHost& ch, int mode, const JacobianIO& io, hipStream_t stream);
+hipError_t launch_evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t stream);
 // Cooperative resident kernel (ikpso_coop.h): io.coop_* describe the grid and workspace.
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream);
 // Co-resident workgroups per CU of the cooperative kernel, CU count, threads per workgroup.

@@ -138,6 +138,14 @@ hipError_t launch_evaluate_jacobian(const ChainHost& ch, int mode, const Jacobia
         ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_jacobian(ch, mode, io, stream); });
 }
 
+hipError_t launch_evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t stream)
+{
+    if (io.n <= 0) return hipSuccess;
+    if (!ch.aux_dev) return hipErrorInvalidValue;
+    return launch_on_topology(
+        ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_gradient(ch, mode, io, stream); });
+}
+
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)
 {
     if (io.num_swarms <= 0) return hipSuccess;

@@ -183,4 +183,21 @@ struct JacobianIO {
     float axis_y_comp[kMaxEffFrames];
 };
 
+// Parameters of the gradient kernel (ikpso_solver_evaluate_gradient): ikpso_solver_evaluate_frames' inputs,
+// the fitness it reports and that fitness's derivative with respect to every free angle out.
+struct GradientIO {
+    const float* angles;      // [n][dfree]
+    const float* targets;     // [n][E][3] or null (chain targets)
+    const float* rest;        // [n][dfree] or null (chain rotations)
+    const float* target_rot;  // [n][E][9] row-major, or null (no weight > 0)
+    float* out_fitness;       // [n] or null
+    float* out_gradient;      // [n][dfree]
+    int64_t n;
+    float rot_w[kMaxEffFrames];  // the caller's weight per effector slot, 0 beyond E
+    // JacobianIO's, filled by run_evaluate_gradient: frame_comp also scales the rotation the rotation term
+    // is formed on (EvalFramesIO::rot_comp)
+    float frame_comp[kMaxEffFrames];
+    float axis_y_comp[kMaxEffFrames];
+};
+
 }  // namespace ikpso

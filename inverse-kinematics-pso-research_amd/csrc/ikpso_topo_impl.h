@@ -1,8 +1,9 @@
 // ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo>,
-// EvalFramesOps<Topo, MODE> and JacobianOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// EvalFramesOps<Topo, MODE>, JacobianOps<Topo, MODE> and GradientOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
+#include "ikpso_gradient.h"
 #include "ikpso_jacobian.h"
 #include "ikpso_resident.h"
 #include "ikpso_stream.h"
@@ -50,6 +51,12 @@ template <class Topo, int MODE>
 hipError_t JacobianOps<Topo, MODE>::evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t s)
 {
     return run_evaluate_jacobian<Topo, MODE>(ch, io, s);
+}
+
+template <class Topo, int MODE>
+hipError_t GradientOps<Topo, MODE>::evaluate(const ChainHost& ch, const GradientIO& io, hipStream_t s)
+{
+    return run_evaluate_gradient<Topo, MODE>(ch, io, s);
 }
 
 template <class Topo, int MODE>

@@ -51,6 +51,13 @@ struct JacobianOps {
     static hipError_t evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t stream);
 };
 
+// The gradient kernels (ikpso_solver_evaluate_gradient; every Euler topology, both modes), likewise
+// (ikpso_inst_gradient_*.hip).
+template <class Topo, int MODE>
+struct GradientOps {
+    static hipError_t evaluate(const ChainHost& ch, const GradientIO& io, hipStream_t stream);
+};
+
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
 // chain use its Euler form.
 template <class Topo>
@@ -105,6 +112,13 @@ struct TopoOps {
             return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
         else
             return with_mode(mode, [&](auto m) { return JacobianOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
+    }
+    static hipError_t evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t s)
+    {
+        if constexpr (Topo::kDH)
+            return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
+        else
+            return with_mode(mode, [&](auto m) { return GradientOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
     static hipError_t coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t s)
     {

@@ -562,6 +562,58 @@ class BatchSolver:
                    "ikpso_solver_evaluate_jacobian")
         return jac, pos
 
+    def gradient(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None, stream=None):
+        """The fitness evaluate_frames() reports and its gradient with respect to the angles
+        (ikpso_solver_evaluate_gradient): (fitness [n], gradient [n, D]).  The arguments are evaluate_frames()'.
+        gradient[i, d] is d fitness[i] / d angles[i, d] over every smooth term of the objective -- effector
+        positions, the distance term, the angle term, the soft-limit penalty and the rotation term -- one
+        column per free dimension in the solver's order.  A pose that collides has fitness FLT_MAX and the
+        gradient of the smooth terms all the same.  Every solver evaluate() serves is served."""
+        torch = _torch()
+        n = int(angles.shape[0])
+        E = self.effectors
+        if tuple(angles.shape) != (n, self.dof):
+            raise ValueError(f"angles must be [n, {self.dof}]")
+        if targets is not None and tuple(targets.shape) != (n, E, 3):
+            raise ValueError(f"targets must be [{n}, {E}, 3]")
+        if rest is not None and tuple(rest.shape) != (n, self.dof):
+            raise ValueError(f"rest must be [{n}, {self.dof}]")
+        if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
+            raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
+        host_w = self._host_weights(effector_rot_weight)
+        for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
+            self._check_tensor(t, name, angles.device)
+        fit = torch.empty((n,), dtype=torch.float32, device=angles.device)
+        grad = torch.empty((n, self.dof), dtype=torch.float32, device=angles.device)
+        _abi.check(self._lib.ikpso_solver_evaluate_gradient(self._h, _dev_ptr(angles), _dev_ptr(targets), _dev_ptr(rest),
+                                                            _dev_ptr(effector_rot), host_w, n, _dev_ptr(fit),
+                                                            _dev_ptr(grad), _stream_handle(stream)),
+                   "ikpso_solver_evaluate_gradient")
+        return fit, grad
+
+    def fitness(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None, stream=None):
+        """gradient()'s fitness [n] as a tensor on the autograd graph of `angles`: one
+        ikpso_solver_evaluate_gradient call in the forward pass, whose gradient the backward pass scales by
+        the incoming grad_output row by row.  Once differentiable, and with respect to `angles` alone (the
+        other inputs get no gradient).  The device layout rules are gradient()'s."""
+        torch = _torch()
+        solver = self
+
+        class _Fitness(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, x):
+                fit, grad = solver.gradient(x.detach(), targets, rest, effector_rot, effector_rot_weight, stream)
+                ctx.save_for_backward(grad)
+                return fit
+
+            @staticmethod
+            @torch.autograd.function.once_differentiable
+            def backward(ctx, grad_output):
+                (grad,) = ctx.saved_tensors
+                return grad_output[:, None] * grad
+
+        return _Fitness.apply(angles)
+
     def close(self) -> None:
         if getattr(self, "_h", None):
             self._lib.ikpso_solver_destroy(self._h)
