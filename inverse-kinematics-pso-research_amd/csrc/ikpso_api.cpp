@@ -661,6 +661,18 @@ bool effector_weights(const float* rot_weights, int E, float (&slots)[kMaxEffFra
     return true;
 }
 
+// What ikpso_solver_evaluate_frames and ikpso_solver_evaluate_gradient check alike: the solver, the count,
+// the angles and the entry's required outputs (outputs_ok), then the weights into rot_w, then that a
+// weight > 0 -- or an output that reads the targets whatever the weights (reads_target) -- has target_rot.
+bool rot_term_args(const ikpso_solver* s, const float* angles, int64_t n, bool outputs_ok, const float* rot_weights,
+                   const float* target_rot, bool reads_target, float (&rot_w)[kMaxEffFrames])
+{
+    if (!s || n < 0 || (n > 0 && (!angles || !outputs_ok))) return false;
+    bool weighted = false;
+    if (!effector_weights(rot_weights, s->chain.E, rot_w, &weighted)) return false;
+    return target_rot || !(weighted || reads_target);
+}
+
 // What the four track entries share, and the order of their answers (DESIGN, "The track entries' status
 // ladder"): every invalid argument, the common ones here and then the entry's own; a solver the entry does
 // not serve; the empty call; then begin_solve and the launch.  term_checks(term) is the entry's part: it
@@ -1134,12 +1146,10 @@ ikpso_status ikpso_solver_evaluate_frames(ikpso_solver* s, const float* angles, 
                                           int64_t n, float* out_fitness, float* out_positions, float* out_rotations,
                                           float* out_rot_error, void* stream)
 {
-    if (!s || n < 0 || (n > 0 && !angles)) return IKPSO_ERR_INVALID_ARG;
     EvalFramesIO io{};
+    if (!rot_term_args(s, angles, n, true, rot_weights, target_rot, out_rot_error != nullptr, io.rot_w))
+        return IKPSO_ERR_INVALID_ARG;
     io.e = EvalIO{angles, targets, rest, out_fitness, out_positions, n};
-    bool weighted = false;
-    if (!effector_weights(rot_weights, s->chain.E, io.rot_w, &weighted)) return IKPSO_ERR_INVALID_ARG;
-    if ((weighted || out_rot_error) && !target_rot) return IKPSO_ERR_INVALID_ARG;
     io.target_rot = target_rot;
     io.out_rotations = out_rotations;
     io.out_rot_error = out_rot_error;
@@ -1168,11 +1178,9 @@ ikpso_status ikpso_solver_evaluate_gradient(ikpso_solver* s, const float* angles
                                             const float* rest, const float* target_rot, const float* rot_weights,
                                             int64_t n, float* out_fitness, float* out_gradient, void* stream)
 {
-    if (!s || n < 0 || (n > 0 && (!angles || !out_gradient))) return IKPSO_ERR_INVALID_ARG;
     GradientIO io{};
-    bool weighted = false;
-    if (!effector_weights(rot_weights, s->chain.E, io.rot_w, &weighted)) return IKPSO_ERR_INVALID_ARG;
-    if (weighted && !target_rot) return IKPSO_ERR_INVALID_ARG;
+    if (!rot_term_args(s, angles, n, out_gradient != nullptr, rot_weights, target_rot, false, io.rot_w))
+        return IKPSO_ERR_INVALID_ARG;
     io.angles = angles;
     io.targets = targets;
     io.rest = rest;

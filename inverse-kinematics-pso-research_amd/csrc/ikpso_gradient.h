@@ -9,51 +9,9 @@
 
 #include <hip/hip_runtime.h>
 
-#include "ikpso_resident.h"
+#include "ikpso_evaluate.h"
 
 namespace ikpso {
-
-struct Vec3 {
-    float x, y, z;
-};
-
-// a x b and a . b.  REFERENCE: no FMA contraction, so the written order is the rounding.
-template <int MODE>
-__device__ __forceinline__ Vec3 cross3(const Vec3& a, const Vec3& b)
-{
-    if constexpr (MODE == IKPSO_ARITH_REFERENCE) {
-#pragma clang fp contract(off)
-        return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-    } else {
-#pragma clang fp contract(fast)
-        return Vec3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-    }
-}
-template <int MODE>
-__device__ __forceinline__ float dot3(const Vec3& a, const Vec3& b)
-{
-    if constexpr (MODE == IKPSO_ARITH_REFERENCE) {
-#pragma clang fp contract(off)
-        return (a.x * b.x + a.y * b.y) + a.z * b.z;
-    } else {
-#pragma clang fp contract(fast)
-        return (a.x * b.x + a.y * b.y) + a.z * b.z;
-    }
-}
-// a + s b
-template <int MODE>
-__device__ __forceinline__ Vec3 axpy3(const Vec3& a, float s, const Vec3& b)
-{
-    if constexpr (MODE == IKPSO_ARITH_REFERENCE) {
-#pragma clang fp contract(off)
-        return Vec3{a.x + s * b.x, a.y + s * b.y, a.z + s * b.z};
-    } else {
-#pragma clang fp contract(fast)
-        return Vec3{a.x + s * b.x, a.y + s * b.y, a.z + s * b.z};
-    }
-}
-__device__ __forceinline__ Vec3 sub3(const Vec3& a, const Vec3& b) { return Vec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Vec3 add3(const Vec3& a, const Vec3& b) { return Vec3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 
 // v(W T^T) = (M32 - M23, M13 - M31, M21 - M12) of M = W T^T, T row-major at q: the rows of W against the rows
 // of T.  d|W - T|_F^2 / d theta = 2 a . v(W T^T) for dW / d theta = [a]x W, T orthonormal or not.
@@ -166,14 +124,7 @@ __global__ void __launch_bounds__(256) k_evaluate_gradient(const ChainConsts<Top
                 for (int e = 0; e < kMaxEffFrames; ++e) rw = s == e ? gio.rot_w[e] : rw;
                 if (rw > 0.0f) {  // a weight of 0 never reads its target
                     Frame W = acc.F[k];
-                    if constexpr (kComp) {
-                        const float c = gio.frame_comp[k - 1];
-                        W.r00 = __builtin_fmaf(W.r00, c, W.r00), W.r01 = __builtin_fmaf(W.r01, c, W.r01);
-                        W.r02 = __builtin_fmaf(W.r02, c, W.r02), W.r10 = __builtin_fmaf(W.r10, c, W.r10);
-                        W.r11 = __builtin_fmaf(W.r11, c, W.r11), W.r12 = __builtin_fmaf(W.r12, c, W.r12);
-                        W.r20 = __builtin_fmaf(W.r20, c, W.r20), W.r21 = __builtin_fmaf(W.r21, c, W.r21);
-                        W.r22 = __builtin_fmaf(W.r22, c, W.r22);
-                    }
+                    if constexpr (kComp) scale_up(W, gio.frame_comp[k - 1]);
                     const float* q = gio.target_rot + (n * cc.num_eff + s) * 9;
                     const float e2 = frame_rot_error<MODE>(W, q);
                     if constexpr (MODE == IKPSO_ARITH_REFERENCE) {
@@ -189,8 +140,7 @@ __global__ void __launch_bounds__(256) k_evaluate_gradient(const ChainConsts<Top
             wf[k] = g;
             wm[k] = add3(cross3<MODE>(sub3(p, o), g), torque);
         }
-        // added last; a fitness the collider block set to FLT_MAX stays FLT_MAX
-        if (!((TERMS & kTermColliders) && f == FLT_MAX)) f = f + orient;
+        f = add_last<TERMS>(f, orient);
         if (gio.out_fitness) gio.out_fitness[n] = f;
         // the reverse sweep
         const float aw2 = 2.0f * angle_weight<TERMS>(cc), lw2 = 2.0f * limit_weight<TERMS>(cc);
@@ -246,22 +196,10 @@ __global__ void __launch_bounds__(256) k_evaluate_gradient(const ChainConsts<Top
     }
 }
 
-// ikpso_solver_evaluate_gradient: run_evaluate's grid and routing rule on the gradient kernel.
-template <class Topo, int MODE>
-inline hipError_t run_evaluate_gradient(const ChainHost& ch, const GradientIO& caller_io, hipStream_t stream)
-{
-    static_assert(!Topo::kDH, "the solver evaluates through its Euler chain");
-    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
-    GradientIO io = caller_io;
-    int depth[Topo::J + 1];
-    node_depths<Topo::J>(ch, depth);
-    for (int k = 1; k <= Topo::J; ++k) {
-        io.frame_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
-        io.axis_y_comp[k - 1] = (float)((2.0 * depth[k] - 1.0) * kHwTrigAmplitudeBias);
-    }
-    return launch_evaluate_build(ch, io.n, [&](auto t, dim3 grid, dim3 threads) {
-        hipLaunchKernelGGL((k_evaluate_gradient<Topo, MODE, decltype(t)::value>), grid, threads, 0, stream, cc, io);
-    });
-}
+// ikpso_solver_evaluate_gradient's evaluator kind (run_evaluate_kind).
+struct EvalGradient : EvalAxes<GradientIO> {
+    template <class Topo, int MODE, int TERMS>
+    static constexpr auto kernel() { return &k_evaluate_gradient<Topo, MODE, TERMS>; }
+};
 
 }  // namespace ikpso

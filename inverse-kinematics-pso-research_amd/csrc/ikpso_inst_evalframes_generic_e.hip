@@ -1,11 +1,3 @@
 // ikpso_inst_evalframes_generic_e.hip -- the evaluate kernels with node rotations (ikpso_solver_evaluate_frames) of generic trees of 19-20 joints.
-#include "ikpso_topo_impl.h"
-
-namespace ikpso {
-#if IKPSO_WITH_OTHERS
-template struct EvalFramesOps<TopoGeneric<19>, IKPSO_ARITH_FAST>;
-template struct EvalFramesOps<TopoGeneric<19>, IKPSO_ARITH_REFERENCE>;
-template struct EvalFramesOps<TopoGeneric<20>, IKPSO_ARITH_FAST>;
-template struct EvalFramesOps<TopoGeneric<20>, IKPSO_ARITH_REFERENCE>;
-#endif
-}  // namespace ikpso
+#define IKPSO_EVAL_KIND EvalFrames
+#include "ikpso_evallist_generic_e.h"

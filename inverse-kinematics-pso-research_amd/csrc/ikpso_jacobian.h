@@ -7,7 +7,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "ikpso_resident.h"
+#include "ikpso_evaluate.h"
 
 namespace ikpso {
 
@@ -45,18 +45,11 @@ __device__ __forceinline__ void store_columns(const CC& cc, float* o, int64_t DF
     for (int c = 0; c < 3; ++c) {
         if (!((fm >> c) & 1u)) continue;
         const float a0 = ax.a[c][0], a1 = ax.a[c][1], a2 = ax.a[c][2];
-        float l0, l1, l2;
-        if constexpr (MODE == IKPSO_ARITH_REFERENCE) {
-#pragma clang fp contract(off)
-            l0 = a1 * dz - a2 * dy, l1 = a2 * dx - a0 * dz, l2 = a0 * dy - a1 * dx;
-        } else {
-#pragma clang fp contract(fast)
-            l0 = a1 * dz - a2 * dy, l1 = a2 * dx - a0 * dz, l2 = a0 * dy - a1 * dx;
-        }
+        const Vec3 l = cross3<MODE>(Vec3{a0, a1, a2}, Vec3{dx, dy, dz});
         float* q = o + dim_rank(cc, 3 * (k - 1) + c);
-        q[0 * DF] = on ? l0 : 0.0f;
-        q[1 * DF] = on ? l1 : 0.0f;
-        q[2 * DF] = on ? l2 : 0.0f;
+        q[0 * DF] = on ? l.x : 0.0f;
+        q[1 * DF] = on ? l.y : 0.0f;
+        q[2 * DF] = on ? l.z : 0.0f;
         q[3 * DF] = on ? a0 : 0.0f;
         q[4 * DF] = on ? a1 : 0.0f;
         q[5 * DF] = on ? a2 : 0.0f;
@@ -178,22 +171,10 @@ __global__ void __launch_bounds__(256) k_evaluate_jacobian(const ChainConsts<Top
     }
 }
 
-// ikpso_solver_evaluate_jacobian: run_evaluate's grid and routing rule on the Jacobian kernel.
-template <class Topo, int MODE>
-inline hipError_t run_evaluate_jacobian(const ChainHost& ch, const JacobianIO& caller_io, hipStream_t stream)
-{
-    static_assert(!Topo::kDH, "the solver evaluates through its Euler chain");
-    const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
-    JacobianIO io = caller_io;
-    int depth[Topo::J + 1];
-    node_depths<Topo::J>(ch, depth);
-    for (int k = 1; k <= Topo::J; ++k) {
-        io.frame_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
-        io.axis_y_comp[k - 1] = (float)((2.0 * depth[k] - 1.0) * kHwTrigAmplitudeBias);
-    }
-    return launch_evaluate_build(ch, io.n, [&](auto t, dim3 grid, dim3 threads) {
-        hipLaunchKernelGGL((k_evaluate_jacobian<Topo, MODE, decltype(t)::value>), grid, threads, 0, stream, cc, io);
-    });
-}
+// ikpso_solver_evaluate_jacobian's evaluator kind (run_evaluate_kind).
+struct EvalJacobian : EvalAxes<JacobianIO> {
+    template <class Topo, int MODE, int TERMS>
+    static constexpr auto kernel() { return &k_evaluate_jacobian<Topo, MODE, TERMS>; }
+};
 
 }  // namespace ikpso

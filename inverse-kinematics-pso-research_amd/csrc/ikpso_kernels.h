@@ -111,7 +111,7 @@ struct EvalFramesIO {
     float* out_rotations;     // [n][J][9] row-major world rotation of nodes 1..J, or null
     float* out_rot_error;     // [n][E] unweighted |R - target|_F^2, or null
     float rot_w[kMaxEffFrames];  // the caller's weight per effector slot, 0 beyond E
-    // 2 depth(k) eps at k - 1 (kHwTrigAmplitudeBias; run_evaluate_frames fills it): what the builds on the
+    // 2 depth(k) eps at k - 1 (kHwTrigAmplitudeBias; run_evaluate_kind fills it): what the builds on the
     // transcendental unit's sin/cos add back to node k's rotation, as ChainConsts::len_hw does to its link
     float rot_comp[kMaxEffFrames];
 };

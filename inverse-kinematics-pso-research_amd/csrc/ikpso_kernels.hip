@@ -21,6 +21,8 @@
 #include "ikpso_kernels.h"
 #include "ikpso_swarm.h"
 #include "ikpso_coop.h"
+#include "ikpso_gradient.h"
+#include "ikpso_jacobian.h"
 #include "ikpso_topo_ops.h"
 
 namespace ikpso {
@@ -122,28 +124,29 @@ hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipS
     return launch_on_topology(ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate(ch, mode, io, stream); });
 }
 
-hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream)
+// The evaluators with units of their own (EvalOps; Kind: ikpso_evaluate.h).
+template <class Kind>
+static hipError_t launch_evaluate_kind(const ChainHost& ch, int mode, const typename Kind::IO& io, hipStream_t stream)
 {
-    if (io.e.n <= 0) return hipSuccess;
+    if (Kind::n(io) <= 0) return hipSuccess;
     if (!ch.aux_dev) return hipErrorInvalidValue;
     return launch_on_topology(
-        ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_frames(ch, mode, io, stream); });
+        ch, [&](auto topo) { return TopoOps<decltype(topo)>::template evaluate_kind<Kind>(ch, mode, io, stream); });
+}
+
+hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream)
+{
+    return launch_evaluate_kind<EvalFrames>(ch, mode, io, stream);
 }
 
 hipError_t launch_evaluate_jacobian(const ChainHost& ch, int mode, const JacobianIO& io, hipStream_t stream)
 {
-    if (io.n <= 0) return hipSuccess;
-    if (!ch.aux_dev) return hipErrorInvalidValue;
-    return launch_on_topology(
-        ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_jacobian(ch, mode, io, stream); });
+    return launch_evaluate_kind<EvalJacobian>(ch, mode, io, stream);
 }
 
 hipError_t launch_evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t stream)
 {
-    if (io.n <= 0) return hipSuccess;
-    if (!ch.aux_dev) return hipErrorInvalidValue;
-    return launch_on_topology(
-        ch, [&](auto topo) { return TopoOps<decltype(topo)>::evaluate_gradient(ch, mode, io, stream); });
+    return launch_evaluate_kind<EvalGradient>(ch, mode, io, stream);
 }
 
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)

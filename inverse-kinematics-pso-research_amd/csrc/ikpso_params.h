@@ -176,7 +176,7 @@ struct JacobianIO {
     float* out_jacobian;   // [n][E][6][dfree]: rows 0..2 linear, 3..5 angular, world coordinates
     int64_t n;
     // The builds on the transcendental unit's sin/cos scale the joint axes back to unit length
-    // (run_evaluate_jacobian fills both, at k - 1): frame_comp is EvalFramesIO::rot_comp, 2 depth(k) eps, for
+    // (run_evaluate_kind fills both, at k - 1): frame_comp is EvalFramesIO::rot_comp, 2 depth(k) eps, for
     // the axes that are columns of a node's frame; axis_y_comp is (2 depth(k) - 1) eps, for node k's y axis,
     // a column of the parent's frame turned by the node's Rx alone.
     float frame_comp[kMaxEffFrames];
@@ -194,7 +194,7 @@ struct GradientIO {
     float* out_gradient;      // [n][dfree]
     int64_t n;
     float rot_w[kMaxEffFrames];  // the caller's weight per effector slot, 0 beyond E
-    // JacobianIO's, filled by run_evaluate_gradient: frame_comp also scales the rotation the rotation term
+    // JacobianIO's, filled by run_evaluate_kind: frame_comp also scales the rotation the rotation term
     // is formed on (EvalFramesIO::rot_comp)
     float frame_comp[kMaxEffFrames];
     float axis_y_comp[kMaxEffFrames];

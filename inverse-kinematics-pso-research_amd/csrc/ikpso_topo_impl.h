@@ -1,8 +1,10 @@
-// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo>,
-// EvalFramesOps<Topo, MODE>, JacobianOps<Topo, MODE> and GradientOps<Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit instantiations.
+// ikpso_topo_impl.h -- definitions of ModeOps<Topo, MODE>, TrackOps<Topo, MODE>, TermTrackOps<TERM, Topo>
+// and EvalOps<Kind, Topo, MODE>; include from the ikpso_inst_*.hip translation units, followed by explicit
+// instantiations.
 #pragma once
 
 #include "ikpso_coop.h"
+#include "ikpso_evaluate.h"
 #include "ikpso_gradient.h"
 #include "ikpso_jacobian.h"
 #include "ikpso_resident.h"
@@ -41,23 +43,17 @@ hipError_t ModeOps<Topo, MODE>::evaluate(const ChainHost& ch, const EvalIO& io, 
     return run_evaluate<Topo, MODE>(ch, io, s);
 }
 
-template <class Topo, int MODE>
-hipError_t EvalFramesOps<Topo, MODE>::evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t s)
+template <class Kind, class Topo, int MODE>
+hipError_t EvalOps<Kind, Topo, MODE>::evaluate(const ChainHost& ch, const typename Kind::IO& io, hipStream_t s)
 {
-    return run_evaluate_frames<Topo, MODE>(ch, io, s);
+    return run_evaluate_kind<Kind, Topo, MODE>(ch, io, s);
 }
 
-template <class Topo, int MODE>
-hipError_t JacobianOps<Topo, MODE>::evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t s)
-{
-    return run_evaluate_jacobian<Topo, MODE>(ch, io, s);
-}
-
-template <class Topo, int MODE>
-hipError_t GradientOps<Topo, MODE>::evaluate(const ChainHost& ch, const GradientIO& io, hipStream_t s)
-{
-    return run_evaluate_gradient<Topo, MODE>(ch, io, s);
-}
+// A unit's evaluate kernels of one topology, both arithmetic modes (the ikpso_evallist_*.h lists; the unit
+// defines IKPSO_EVAL_KIND).
+#define IKPSO_EVAL_INST(...)                                                      \
+    template struct EvalOps<IKPSO_EVAL_KIND, __VA_ARGS__, IKPSO_ARITH_FAST>; \
+    template struct EvalOps<IKPSO_EVAL_KIND, __VA_ARGS__, IKPSO_ARITH_REFERENCE>;
 
 template <class Topo, int MODE>
 hipError_t ModeOps<Topo, MODE>::coop(const ChainHost& ch, const SwarmIO& io, hipStream_t s)

@@ -1,7 +1,8 @@
 // ikpso_topo_ops.h -- per-topology launch entry points.  The kernel templates
-// (ikpso_resident.h, ikpso_stream.h) are instantiated per (topology, mode) in
+// (ikpso_resident.h, ikpso_stream.h, ikpso_evaluate.h) are instantiated per (topology, mode) in
 // their own translation units (ikpso_inst_*.hip) so the build parallelises;
-// the dispatcher (ikpso_kernels.hip) sees only these declarations.
+// the dispatcher (ikpso_kernels.hip) instantiates none of them: it calls these
+// declarations, and reads the evaluator kinds' names from the kernels' headers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -37,25 +38,14 @@ struct TermTrackOps {
     static hipError_t track(const ChainHost& ch, const SwarmIO& io, int block, hipStream_t stream);
 };
 
-// The evaluate kernels that also report the node rotations and the rotation error
-// (ikpso_solver_evaluate_frames; every Euler topology, both modes), likewise (ikpso_inst_evalframes_*.hip).
-template <class Topo, int MODE>
-struct EvalFramesOps {
-    static hipError_t evaluate(const ChainHost& ch, const EvalFramesIO& io, hipStream_t stream);
-};
-
-// The Jacobian kernels (ikpso_solver_evaluate_jacobian; every Euler topology, both modes), likewise
-// (ikpso_inst_jacobian_*.hip).
-template <class Topo, int MODE>
-struct JacobianOps {
-    static hipError_t evaluate(const ChainHost& ch, const JacobianIO& io, hipStream_t stream);
-};
-
-// The gradient kernels (ikpso_solver_evaluate_gradient; every Euler topology, both modes), likewise
-// (ikpso_inst_gradient_*.hip).
-template <class Topo, int MODE>
-struct GradientOps {
-    static hipError_t evaluate(const ChainHost& ch, const GradientIO& io, hipStream_t stream);
+// The evaluate kernels with units of their own (every Euler topology, both modes), likewise.  Kind
+// (ikpso_evaluate.h; ikpso_jacobian.h, ikpso_gradient.h) names the parameter block and the kernel:
+//   EvalOps<EvalFrames, ...>     ikpso_solver_evaluate_frames    ikpso_inst_evalframes_*.hip
+//   EvalOps<EvalJacobian, ...>   ikpso_solver_evaluate_jacobian  ikpso_inst_jacobian_*.hip
+//   EvalOps<EvalGradient, ...>   ikpso_solver_evaluate_gradient  ikpso_inst_gradient_*.hip
+template <class Kind, class Topo, int MODE>
+struct EvalOps {
+    static hipError_t evaluate(const ChainHost& ch, const typename Kind::IO& io, hipStream_t stream);
 };
 
 // The folded chain (TopoDH) has FAST kernels only: REFERENCE runs of such a
@@ -99,26 +89,13 @@ struct TopoOps {
     {
         return with_mode(mode, [&](auto m) { return ModeOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
-    static hipError_t evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t s)
+    template <class Kind>
+    static hipError_t evaluate_kind(const ChainHost& ch, int mode, const typename Kind::IO& io, hipStream_t s)
     {
         if constexpr (Topo::kDH)
             return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
         else
-            return with_mode(mode, [&](auto m) { return EvalFramesOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
-    }
-    static hipError_t evaluate_jacobian(const ChainHost& ch, int mode, const JacobianIO& io, hipStream_t s)
-    {
-        if constexpr (Topo::kDH)
-            return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
-        else
-            return with_mode(mode, [&](auto m) { return JacobianOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
-    }
-    static hipError_t evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t s)
-    {
-        if constexpr (Topo::kDH)
-            return hipErrorNotSupported;  // the solver evaluates through its Euler chain (run_evaluate)
-        else
-            return with_mode(mode, [&](auto m) { return GradientOps<Topo, decltype(m)::value>::evaluate(ch, io, s); });
+            return with_mode(mode, [&](auto m) { return EvalOps<Kind, Topo, decltype(m)::value>::evaluate(ch, io, s); });
     }
     static hipError_t coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t s)
     {

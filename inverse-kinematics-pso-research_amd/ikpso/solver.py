@@ -506,6 +506,23 @@ class BatchSolver:
                    "ikpso_solver_evaluate")
         return fit, pos
 
+    def _evaluate_inputs(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None):
+        """The input checks of evaluate_frames(), gradient() and (angles alone) jacobian(): the shapes, the host
+        weights, then the device layout.  Returns (n, the weights as _host_weights gives them)."""
+        n, E = int(angles.shape[0]), self.effectors
+        if tuple(angles.shape) != (n, self.dof):
+            raise ValueError(f"angles must be [n, {self.dof}]")
+        if targets is not None and tuple(targets.shape) != (n, E, 3):
+            raise ValueError(f"targets must be [{n}, {E}, 3]")
+        if rest is not None and tuple(rest.shape) != (n, self.dof):
+            raise ValueError(f"rest must be [{n}, {self.dof}]")
+        if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
+            raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
+        host_w = self._host_weights(effector_rot_weight)
+        for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
+            self._check_tensor(t, name, angles.device)
+        return n, host_w
+
     def evaluate_frames(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None,
                         stream=None):
         """evaluate() with the node rotations and the orientation objective (ikpso_solver_evaluate_frames):
@@ -518,19 +535,8 @@ class BatchSolver:
         last: the fitness solve_track(effector_rot=...) minimises, and with E = 1 the one
         solve_track(target_rot=..., orientation_weight=...) does.  Every solver evaluate() serves is served."""
         torch = _torch()
-        n = int(angles.shape[0])
         E, J = self.effectors, self.chain.shape[0] - 1
-        if tuple(angles.shape) != (n, self.dof):
-            raise ValueError(f"angles must be [n, {self.dof}]")
-        if targets is not None and tuple(targets.shape) != (n, E, 3):
-            raise ValueError(f"targets must be [{n}, {E}, 3]")
-        if rest is not None and tuple(rest.shape) != (n, self.dof):
-            raise ValueError(f"rest must be [{n}, {self.dof}]")
-        if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
-            raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
-        host_w = self._host_weights(effector_rot_weight)
-        for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
-            self._check_tensor(t, name, angles.device)
+        n, host_w = self._evaluate_inputs(angles, targets, rest, effector_rot, effector_rot_weight)
         fit = torch.empty((n,), dtype=torch.float32, device=angles.device)
         pos = torch.empty((n, J, 3), dtype=torch.float32, device=angles.device)
         rot = torch.empty((n, J, 3, 3), dtype=torch.float32, device=angles.device)
@@ -550,11 +556,8 @@ class BatchSolver:
         order as in targets; a dimension off the effector's path to the root has a column of zeros.
         manipulability() takes the result.  Every solver evaluate() serves is served."""
         torch = _torch()
-        n = int(angles.shape[0])
         E, J = self.effectors, self.chain.shape[0] - 1
-        if tuple(angles.shape) != (n, self.dof):
-            raise ValueError(f"angles must be [n, {self.dof}]")
-        self._check_tensor(angles, "angles", angles.device)
+        n, _ = self._evaluate_inputs(angles)
         jac = torch.empty((n, E, 6, self.dof), dtype=torch.float32, device=angles.device)
         pos = torch.empty((n, J, 3), dtype=torch.float32, device=angles.device)
         _abi.check(self._lib.ikpso_solver_evaluate_jacobian(self._h, _dev_ptr(angles), n, _dev_ptr(pos), _dev_ptr(jac),
@@ -570,19 +573,7 @@ class BatchSolver:
         column per free dimension in the solver's order.  A pose that collides has fitness FLT_MAX and the
         gradient of the smooth terms all the same.  Every solver evaluate() serves is served."""
         torch = _torch()
-        n = int(angles.shape[0])
-        E = self.effectors
-        if tuple(angles.shape) != (n, self.dof):
-            raise ValueError(f"angles must be [n, {self.dof}]")
-        if targets is not None and tuple(targets.shape) != (n, E, 3):
-            raise ValueError(f"targets must be [{n}, {E}, 3]")
-        if rest is not None and tuple(rest.shape) != (n, self.dof):
-            raise ValueError(f"rest must be [{n}, {self.dof}]")
-        if effector_rot is not None and tuple(effector_rot.shape) != (n, E, 3, 3):
-            raise ValueError(f"effector_rot must be [{n}, {E}, 3, 3]")
-        host_w = self._host_weights(effector_rot_weight)
-        for t, name in ((angles, "angles"), (targets, "targets"), (rest, "rest"), (effector_rot, "effector_rot")):
-            self._check_tensor(t, name, angles.device)
+        n, host_w = self._evaluate_inputs(angles, targets, rest, effector_rot, effector_rot_weight)
         fit = torch.empty((n,), dtype=torch.float32, device=angles.device)
         grad = torch.empty((n, self.dof), dtype=torch.float32, device=angles.device)
         _abi.check(self._lib.ikpso_solver_evaluate_gradient(self._h, _dev_ptr(angles), _dev_ptr(targets), _dev_ptr(rest),
