@@ -592,6 +592,46 @@ ikpso_status ikpso_solver_evaluate_gradient(ikpso_solver* solver, const float* a
                                             const float* rest, const float* target_rot, const float* rot_weights,
                                             int64_t n, float* out_fitness, float* out_gradient, void* stream);
 
+/* Which node of given angle vectors hits which collider, on the device (added after ABI 5;
+ * detect by symbol): the decisions behind a fitness of FLT_MAX -- the collider term makes them
+ * per node and per collider and the fitness keeps only "some pair hit".  A planner scoring
+ * poses learns which obstacle to route around, a caller whose answer came back FLT_MAX
+ * whether the wrist or the elbow is stuck, a track caller at which frame and node contact
+ * starts.
+ *   angles         exactly ikpso_solver_evaluate_jacobian's: device, [n][D], the free
+ *                  dimensions under an axis mask, locked axes at the chain's rotation, always
+ *                  the Euler form of the chain.
+ *   out_contacts   device, [n][C] uint32_t, C the collider_count of the descriptor the solver
+ *                  was created with -- the caller's own indexing, the colliders the solver
+ *                  left out as beyond the arm's reach (ikpso_solver_collider_count) included:
+ *                  their columns are all zero.  Bit k - 1 of out_contacts[i][c] is set exactly
+ *                  when node k's node box or link box is decided to intersect collider c at
+ *                  vector i; J <= 20, so bits J .. 31 are 0.  Required when n > 0 and C > 0;
+ *                  may be NULL when C == 0.
+ *   out_positions  device, [n][J][3] or NULL: ikpso_solver_evaluate's positions (FAST: with
+ *                  the caveat ikpso_solver_evaluate_frames states).
+ * No targets, rest pose or weights: contacts depend on none of them.
+ * Definition.  The boxes are the collider term's: the node box is a cube of edge 0.2 (the
+ * reference's GIZMO_SIZE) at the node, the link box is length_k x 0.05 x 0.05 centred between
+ * the node and its parent, both oriented by the node's world rotation R_k.  The decision is the
+ * one the solver's own kernels make for this chain: REFERENCE decides by the reference's GJK,
+ * bit for bit; FAST decides by the separating-axis test where its solve kernels do, and by GJK
+ * where they do (a chain with an axis mask or with angle bounds beyond the hardware sin/cos
+ * range, a generic tree, a collider whose quaternion is no rotation).  Every pair of a node and
+ * a collider is decided -- nothing stops at a first hit -- and both boxes of a pair are OR-ed
+ * into its bit.
+ * Contract with ikpso_solver_evaluate, in both arithmetics and exactly: for the same solver
+ * and angles and any targets, some word of out_contacts[i] is non-zero if and only if
+ * out_fitness[i] == FLT_MAX.
+ * Served is every solver ikpso_solver_evaluate serves, routed as evaluate routes it.  A
+ * solver with no collider within reach (none given, or all left out) has nothing to decide:
+ * out_contacts is zeroed in stream order and out_positions is ikpso_solver_evaluate's.
+ * IKPSO_ERR_INVALID_ARG: a NULL solver; n < 0; n > 0 with a NULL angles; n > 0 and C > 0
+ * with a NULL out_contacts.  n == 0 is IKPSO_OK with no device work.  Stream-ordered: the
+ * call does not synchronise, and it neither waits for nor settles a pending solve. */
+ikpso_status ikpso_solver_evaluate_contacts(ikpso_solver* solver, const float* angles, int64_t n,
+                                            uint32_t* out_contacts, float* out_positions, void* stream);
+
 /* Copy the generator states of local swarms [first_swarm, first_swarm + count)
  * (P states each, swarm-major, 48-byte curandState layout) into dst (any memory,
  * count * P states), after settling a pending solve (ABI >= 5).  Synchronises

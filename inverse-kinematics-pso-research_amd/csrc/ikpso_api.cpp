@@ -905,7 +905,14 @@ ikpso_status ikpso_solver_create(const ikpso_solver_desc* desc, ikpso_solver** o
         const hipError_t e = hipMalloc(dev, bytes);
         return e == hipSuccess ? hipMemcpy(*dev, host.data(), bytes, hipMemcpyHostToDevice) : e;
     };
-    hipError_t e = upload(&s->aux, s->chain.aux);
+    // the Euler chain's aux with the kept colliders' indices behind it (ChainHost::coll_index)
+    std::vector<float> aux_idx = s->chain.aux;
+    aux_idx.resize(s->chain.aux.size() + s->chain.coll_index.size());
+    for (size_t j = 0; j < s->chain.coll_index.size(); ++j) {
+        const int32_t index = s->chain.coll_index[j];
+        memcpy(&aux_idx[s->chain.aux.size() + j], &index, sizeof(index));
+    }
+    hipError_t e = upload(&s->aux, aux_idx);
     if (e == hipSuccess && s->use_dh) e = upload(&s->aux_dh, s->dhchain.aux);
     if (e != hipSuccess) return fail(hip_status(e));
     s->chain.aux_dev = s->aux;
@@ -1189,6 +1196,37 @@ ikpso_status ikpso_solver_evaluate_gradient(ikpso_solver* s, const float* angles
     io.out_gradient = out_gradient;
     io.n = n;
     IKPSO_HIP(launch_evaluate_gradient(s->chain, s->mode, io, (hipStream_t)stream));
+    return IKPSO_OK;
+}
+
+// ikpso_solver_evaluate_jacobian's angle vectors on the contacts kernels: every solver evaluate serves.  One
+// word per vector and collider of the caller's descriptor; a solver whose colliders were all pruned (or that
+// was given none) has nothing to decide: zeros, and the positions from the plain evaluate kernel.
+ikpso_status ikpso_solver_evaluate_contacts(ikpso_solver* s, const float* angles, int64_t n, uint32_t* out_contacts,
+                                            float* out_positions, void* stream)
+{
+    if (!s || n < 0 || (n > 0 && (!angles || (s->chain.coll_given > 0 && !out_contacts))))
+        return IKPSO_ERR_INVALID_ARG;
+    if (n == 0) return IKPSO_OK;
+    const hipStream_t hs = (hipStream_t)stream;
+    const ChainHost& ch = s->chain;
+    if (ch.num_coll == 0) {
+        if (ch.coll_given > 0)
+            IKPSO_HIP(hipMemsetAsync(out_contacts, 0, sizeof(uint32_t) * (size_t)n * ch.coll_given, hs));
+        if (out_positions) {
+            EvalIO io{angles, nullptr, nullptr, nullptr, out_positions, n};
+            IKPSO_HIP(launch_evaluate(ch, s->mode, io, hs));
+        }
+        return IKPSO_OK;
+    }
+    ContactsIO io{};
+    io.angles = angles;
+    io.out_contacts = out_contacts;
+    io.out_positions = out_positions;
+    io.n = n;
+    io.columns = ch.coll_given;
+    io.column_of = reinterpret_cast<const int32_t*>(s->aux + ch.aux.size());
+    IKPSO_HIP(launch_evaluate_contacts(ch, s->mode, io, hs));
     return IKPSO_OK;
 }
 

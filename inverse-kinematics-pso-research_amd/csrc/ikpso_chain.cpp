@@ -353,6 +353,8 @@ ikpso_status parse_chain(const std::vector<ikpso_node>& nodes, const ikpso_pso_c
     }
     ch.colliders_dropped = nin - (int)kept.size();
     ch.num_coll = (int)kept.size();
+    ch.coll_index = kept;
+    ch.coll_given = nin;
     ch.coll_off = ((size_t)10 * J + 15) & ~size_t(15);
     ch.coll_lim_off = ch.coll_off + (size_t)16 * ch.num_coll;
     ch.coll_box_off = (ch.coll_lim_off + (size_t)J * ch.num_coll + 15) & ~size_t(15);

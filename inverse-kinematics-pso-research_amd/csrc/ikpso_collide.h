@@ -72,6 +72,7 @@ enum {
 #if IKPSO_COLLIDE_STATS
 #define IKPSO_CS_PARAM , unsigned long long* cs
 #define IKPSO_CS_ARG , cs
+#define IKPSO_CS_NONE , nullptr  // a caller that counts nothing (the reporting siblings, ikpso_contacts.h)
 // add the number of active lanes with `pred` to counter i (one atomic per wave)
 __device__ __forceinline__ void cs_count(unsigned long long* cs, int i, bool pred)
 {
@@ -82,6 +83,7 @@ __device__ __forceinline__ void cs_count(unsigned long long* cs, int i, bool pre
 #else
 #define IKPSO_CS_PARAM
 #define IKPSO_CS_ARG
+#define IKPSO_CS_NONE
 #endif
 constexpr float kGizmo = 0.2f;          // GIZMO_SIZE
 
@@ -586,6 +588,102 @@ __device__ __noinline__ bool node_collides(float r00, float r01, float r02, floa
         if (may_touch(b, cb) && gjk_intersect(b, cb IKPSO_CS_ARG)) return true;
     }
     return false;
+}
+
+// ---- reporting siblings (ikpso_solver_evaluate_contacts, ikpso_contacts.h) ----
+// node_collides_obb and node_collides answer "does this node hit anything" and stop at the first hit; these
+// two answer "which colliders does it hit": the same boxes, the same sphere guards (may_touch) and the same
+// box tests in the same arithmetic, every collider decided, no early exit.  Bit i of the result is collider
+// first + i, for the kContactChunk colliders from `first` (the caller steps `first` over the scene), and is
+// the OR of the node box's and the link box's decision -- so the link box of a pair whose node box already
+// hit is not tested: the bit is set either way.  The first kNearUnroll colliders of a chunk sit under
+// uniform guards like near_collider's; the box tests themselves stay in loops (one GJK site, as in
+// node_collides).  Templates, so that a unit that reports no contacts carries no code of theirs.
+constexpr int kContactChunk = 32;
+
+template <int kChunk = kContactChunk>
+__device__ __forceinline__ uint32_t node_contacts_obb(float r00, float r01, float r02, float r10, float r11, float r12,
+                                                      float r20, float r21, float r22, float nx, float ny, float nz,
+                                                      float ex, float ey, float ez, float length, const CollRec* coll,
+                                                      const float* cbox, int first, int count)
+{
+    static_assert(kChunk >= kNearUnroll && kChunk <= 32, "one result word");
+    const float A[9] = {r00, r10, r20, r01, r11, r21, r02, r12, r22};  // the frame's columns
+    const float pn[3] = {nx, ny, nz};
+    const float pl[3] = {(nx + ex) * 0.5f, (ny + ey) * 0.5f, (nz + ez) * 0.5f};
+    const float en[3] = {kGizmo * 0.5f, kGizmo * 0.5f, kGizmo * 0.5f};
+    const float el[3] = {fabsf(length) * 0.5f, kGizmo * 0.125f, kGizmo * 0.125f};
+    const float rn = sphere_radius(kGizmo, kGizmo, kGizmo, kGainBound);
+    const float rl = sphere_radius(length, kGizmo * 0.25f, kGizmo * 0.25f, kGainBound);
+    // which of the chunk's colliders either box may touch: bit 2i the node box, bit 2i + 1 the link box
+    uint64_t guard = 0;
+    auto sphere = [&](int i) {
+        const CollRec& c = coll[first + i];
+        if (may_touch(pn[0], pn[1], pn[2], rn, c.px, c.py, c.pz, c.radius)) guard |= 1ull << (2 * i);
+        if (may_touch(pl[0], pl[1], pl[2], rl, c.px, c.py, c.pz, c.radius)) guard |= 2ull << (2 * i);
+    };
+    const int n = count - first < kChunk ? count - first : kChunk;
+#pragma unroll
+    for (int i = 0; i < kNearUnroll; ++i)
+        if (i < n) sphere(i);
+    for (int i = kNearUnroll; i < n; ++i) sphere(i);
+    uint32_t hits = 0;
+    while (guard != 0) {
+        const int j = __builtin_ctzll(guard);
+        guard &= guard - 1;
+        const int i = j >> 1;
+        if ((hits >> i) & 1u) continue;  // (the node box hit: the pair is decided)
+        const float* bx = cbox + 16 * (first + i);
+        const bool link = j & 1;
+        const float p[3] = {link ? pl[0] : pn[0], link ? pl[1] : pn[1], link ? pl[2] : pn[2]};
+        const float e[3] = {link ? el[0] : en[0], link ? el[1] : en[1], link ? el[2] : en[2]};
+        if (obb_overlap(p, A, e, bx + 12, bx, bx + 9)) hits |= 1u << i;
+    }
+    return hits;
+}
+
+template <int kChunk = kContactChunk>
+__device__ __noinline__ uint32_t node_contacts(float r00, float r01, float r02, float r10, float r11, float r12,
+                                               float r20, float r21, float r22, float nx, float ny, float nz, float ex,
+                                               float ey, float ez, float length, const CollRec* coll, int first,
+                                               int count)
+{
+    static_assert(kChunk >= kNearUnroll && kChunk <= 32, "one result word");
+    float q[4], qi[4];
+    mat_to_quat(r00, r01, r02, r10, r11, r12, r20, r21, r22, q);
+    quat_inverse(q, qi);
+    const float gain = quat_gain(q[0], q[1], q[2], q[3]);
+    const Box nb{nx, ny, nz, q[0], q[1], q[2], q[3], qi[0], qi[1], qi[2], qi[3], kGizmo, kGizmo, kGizmo,
+                 sphere_radius(kGizmo, kGizmo, kGizmo, gain)};
+    const float lw = kGizmo * 0.25f;
+    const Box lb{(nx + ex) * 0.5f, (ny + ey) * 0.5f, (nz + ez) * 0.5f, q[0], q[1], q[2], q[3], qi[0], qi[1], qi[2],
+                 qi[3], length, lw, lw, sphere_radius(length, lw, lw, gain)};
+    uint64_t guard = 0;
+    auto sphere = [&](int i) {
+        const CollRec& c = coll[first + i];
+        if (may_touch(nb.px, nb.py, nb.pz, nb.radius, c.px, c.py, c.pz, c.radius)) guard |= 1ull << (2 * i);
+        if (may_touch(lb.px, lb.py, lb.pz, lb.radius, c.px, c.py, c.pz, c.radius)) guard |= 2ull << (2 * i);
+    };
+    const int n = count - first < kChunk ? count - first : kChunk;
+#pragma unroll
+    for (int i = 0; i < kNearUnroll; ++i)
+        if (i < n) sphere(i);
+    for (int i = kNearUnroll; i < n; ++i) sphere(i);
+    // one GJK site: pair j = (collider j / 2, node box if j even else link box), as node_collides has it
+    uint32_t hits = 0;
+    while (guard != 0) {
+        const int j = __builtin_ctzll(guard);
+        guard &= guard - 1;
+        const int i = j >> 1;
+        if ((hits >> i) & 1u) continue;  // (the node box hit: the pair is decided)
+        const Box cb = box_from_record(coll[first + i]);
+        const bool link = j & 1;
+        const Box b{link ? lb.px : nb.px, link ? lb.py : nb.py, link ? lb.pz : nb.pz, nb.qx, nb.qy, nb.qz, nb.qw,
+                    nb.ix, nb.iy, nb.iz, nb.iw, link ? lb.sx : nb.sx, link ? lb.sy : nb.sy, link ? lb.sz : nb.sz,
+                    link ? lb.radius : nb.radius};
+        if (gjk_intersect(b, cb IKPSO_CS_NONE)) hits |= 1u << i;
+    }
+    return hits;
 }
 
 #pragma clang fp contract(fast)  // the HIP default (-ffp-contract=fast-honor-pragmas)

@@ -1,5 +1,5 @@
 // ikpso_evallist_generic_c.h -- the topologies of the evaluate family's generic_c units (generic trees of 13-16 joints):
-// included by ikpso_inst_{evalframes,jacobian,gradient}_generic_c.hip after each defines IKPSO_EVAL_KIND.
+// included by ikpso_inst_{evalframes,jacobian,gradient,contacts}_generic_c.hip after each defines IKPSO_EVAL_KIND.
 #include "ikpso_topo_impl.h"
 
 namespace ikpso {

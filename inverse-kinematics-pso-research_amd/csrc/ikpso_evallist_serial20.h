@@ -1,5 +1,5 @@
 // ikpso_evallist_serial20.h -- the topologies of the evaluate family's serial20 units (the 20-joint serial chain):
-// included by ikpso_inst_{evalframes,jacobian,gradient}_serial20.hip after each defines IKPSO_EVAL_KIND.
+// included by ikpso_inst_{evalframes,jacobian,gradient,contacts}_serial20.hip after each defines IKPSO_EVAL_KIND.
 #include "ikpso_topo_impl.h"
 
 namespace ikpso {

@@ -1,5 +1,5 @@
 // ikpso_evallist_serial_b.h -- the topologies of the evaluate family's serial_b units (serial chains of 9, 10, 11 joints with a tip effector):
-// included by ikpso_inst_{evalframes,jacobian,gradient}_serial_b.hip after each defines IKPSO_EVAL_KIND.
+// included by ikpso_inst_{evalframes,jacobian,gradient,contacts}_serial_b.hip after each defines IKPSO_EVAL_KIND.
 #include "ikpso_topo_impl.h"
 
 namespace ikpso {

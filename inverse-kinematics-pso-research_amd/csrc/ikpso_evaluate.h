@@ -4,7 +4,8 @@
 //   k_evaluate: FK + fitness of given angle vectors (parity/KAT entry).
 //   k_evaluate_frames: the same with the node rotations, the rotation error per effector and the
 //     rotation term in the fitness (ikpso_solver_evaluate_frames).
-//   k_evaluate_jacobian (ikpso_jacobian.h) and k_evaluate_gradient (ikpso_gradient.h) build on this header.
+//   k_evaluate_jacobian (ikpso_jacobian.h), k_evaluate_gradient (ikpso_gradient.h) and k_evaluate_contacts
+//     (ikpso_contacts.h) build on this header.
 //
 // All four run the same builds on the same grid (launch_evaluate_build).  The three with units of their
 // own go through run_evaluate_kind: an evaluator kind names its parameter block and its kernel.
@@ -264,7 +265,7 @@ inline hipError_t run_evaluate(const ChainHost& ch, const EvalIO& io, hipStream_
     }
 }
 // What the builds on the transcendental unit's sin/cos add back (kHwTrigAmplitudeBias; fp64, rounded once),
-// at k - 1: frame_comp is 2 depth(k) eps, for a column of node k's frame; axis_y_comp (null: not wanted) is
+// at k - 1: frame_comp (null: not wanted) is 2 depth(k) eps, for a column of node k's frame; axis_y_comp (null too) is
 // (2 depth(k) - 1) eps, for node k's y axis, a column of the parent's frame turned by the node's Rx alone.
 template <int J>
 inline void fill_trig_comp(const ChainHost& ch, float* frame_comp, float* axis_y_comp)
@@ -272,16 +273,19 @@ inline void fill_trig_comp(const ChainHost& ch, float* frame_comp, float* axis_y
     int depth[J + 1];
     node_depths<J>(ch, depth);
     for (int k = 1; k <= J; ++k) {
-        frame_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
+        if (frame_comp) frame_comp[k - 1] = (float)(2.0 * depth[k] * kHwTrigAmplitudeBias);
         if (axis_y_comp) axis_y_comp[k - 1] = (float)((2.0 * depth[k] - 1.0) * kHwTrigAmplitudeBias);
     }
 }
 
 // An evaluator kind (EvalOps' Kind) names its parameter block IO, where that block holds the vector count
-// and the compensation arrays, and its kernel.  EvalFrames: ikpso_solver_evaluate_frames; EvalJacobian and
-// EvalGradient stand beside their kernels, on EvalAxes.
+// and the compensation arrays, and its kernel; kPlainBuild, whether it has a kernel for a chain without the
+// collider term (one that has none refuses such a chain: nothing of it is instantiated for the plain term
+// set).  EvalFrames: ikpso_solver_evaluate_frames; EvalJacobian and EvalGradient stand beside their kernels,
+// on EvalAxes; EvalContacts beside its own (ikpso_contacts.h).
 struct EvalFrames {
     using IO = EvalFramesIO;
+    static constexpr bool kPlainBuild = true;
     static int64_t n(const IO& io) { return io.e.n; }
     static float* frame_comp(IO& io) { return io.rot_comp; }
     static float* axis_y_comp(IO&) { return nullptr; }
@@ -291,6 +295,7 @@ struct EvalFrames {
 template <class AxesIO>
 struct EvalAxes {  // the parameter blocks with JacobianIO's joint-axis compensation
     using IO = AxesIO;
+    static constexpr bool kPlainBuild = true;
     static int64_t n(const IO& io) { return io.n; }
     static float* frame_comp(IO& io) { return io.frame_comp; }
     static float* axis_y_comp(IO& io) { return io.axis_y_comp; }
@@ -305,9 +310,15 @@ inline hipError_t run_evaluate_kind(const ChainHost& ch, const typename Kind::IO
     const ChainConsts<Topo::J> cc = make_consts<Topo::J>(ch);
     typename Kind::IO io = caller_io;
     fill_trig_comp<Topo::J>(ch, Kind::frame_comp(io), Kind::axis_y_comp(io));
-    return launch_evaluate_build(ch, Kind::n(io), [&](auto t, dim3 grid, dim3 threads) {
-        hipLaunchKernelGGL((Kind::template kernel<Topo, MODE, decltype(t)::value>()), grid, threads, 0, stream, cc, io);
+    bool refused = false;
+    const hipError_t err = launch_evaluate_build(ch, Kind::n(io), [&](auto t, dim3 grid, dim3 threads) {
+        constexpr int TERMS = decltype(t)::value;
+        if constexpr (Kind::kPlainBuild || (TERMS & kTermColliders))
+            hipLaunchKernelGGL((Kind::template kernel<Topo, MODE, TERMS>()), grid, threads, 0, stream, cc, io);
+        else
+            refused = true;
     });
+    return refused ? hipErrorNotSupported : err;
 }
 
 }  // namespace ikpso

@@ -73,6 +73,11 @@ struct ChainHost {
     size_t coll_off = 0;          // float offset of the collider records in aux
     size_t coll_lim_off = 0;      // ... of near_collider's squared limits [J][num_coll] (after the records)
     size_t coll_box_off = 0;      // ... of the colliders as oriented boxes [num_coll][16] (after the limits)
+    // The caller's index of each collider kept (ascending) and how many the caller gave: the columns
+    // ikpso_solver_evaluate_contacts reports in.  A solver's device copy of aux carries the indices behind
+    // the host copy's regions, as int32 (aux_dev + aux.size(): ContactsIO::column_of).
+    std::vector<int> coll_index;
+    int coll_given = 0;
     bool coll_obb = true;         // every collider's quaternion is a rotation (|q| = 1 to 1e-5): the FAST
                                   // builds may test it as an oriented box (kFastSat); else they take GJK
     // joint-axis mask over the kernel's dimensions (all set: no mask) and the
@@ -282,6 +287,8 @@ hipError_t launch_evaluate(const ChainHost& ch, int mode, const EvalIO& io, hipS
 hipError_t launch_evaluate_frames(const ChainHost& ch, int mode, const EvalFramesIO& io, hipStream_t stream);
 hipError_t launch_evaluate_jacobian(const ChainHost& ch, int mode, const JacobianIO& io, hipStream_t stream);
 hipError_t launch_evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t stream);
+// (a chain with num_coll > 0: without a collider the kernels test there is nothing to decide, and no kernel)
+hipError_t launch_evaluate_contacts(const ChainHost& ch, int mode, const ContactsIO& io, hipStream_t stream);
 // Cooperative resident kernel (ikpso_coop.h): io.coop_* describe the grid and workspace.
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream);
 // Co-resident workgroups per CU of the cooperative kernel, CU count, threads per workgroup.

@@ -21,6 +21,7 @@
 #include "ikpso_kernels.h"
 #include "ikpso_swarm.h"
 #include "ikpso_coop.h"
+#include "ikpso_contacts.h"
 #include "ikpso_gradient.h"
 #include "ikpso_jacobian.h"
 #include "ikpso_topo_ops.h"
@@ -147,6 +148,12 @@ hipError_t launch_evaluate_jacobian(const ChainHost& ch, int mode, const Jacobia
 hipError_t launch_evaluate_gradient(const ChainHost& ch, int mode, const GradientIO& io, hipStream_t stream)
 {
     return launch_evaluate_kind<EvalGradient>(ch, mode, io, stream);
+}
+
+hipError_t launch_evaluate_contacts(const ChainHost& ch, int mode, const ContactsIO& io, hipStream_t stream)
+{
+    if (io.n > 0 && (ch.num_coll <= 0 || !io.out_contacts || !io.column_of)) return hipErrorInvalidValue;
+    return launch_evaluate_kind<EvalContacts>(ch, mode, io, stream);
 }
 
 hipError_t launch_coop(const ChainHost& ch, int mode, const SwarmIO& io, hipStream_t stream)

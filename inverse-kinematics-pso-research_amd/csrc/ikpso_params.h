@@ -200,4 +200,19 @@ struct GradientIO {
     float axis_y_comp[kMaxEffFrames];
 };
 
+// Parameters of the contacts kernel (ikpso_solver_evaluate_contacts): the Jacobian kernel's angle vectors in,
+// per vector one word per collider of the caller's descriptor out -- bit k - 1 set when node k's node box or
+// link box is decided to intersect it.
+struct ContactsIO {
+    const float* angles;     // [n][dfree]
+    uint32_t* out_contacts;  // [n][columns]
+    float* out_positions;    // [n][J][3] or null
+    int64_t n;
+    // The caller's collider count C, and for the kernels' collider c (0 .. num_coll - 1: those within the arm's
+    // reach) its index in the caller's descriptor: ChainHost::coll_index, in aux on the device.  A column that
+    // is no kept collider's is written 0.
+    int32_t columns;
+    const int32_t* column_of;
+};
+
 }  // namespace ikpso

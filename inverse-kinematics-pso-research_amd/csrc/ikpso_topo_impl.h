@@ -3,6 +3,7 @@
 // instantiations.
 #pragma once
 
+#include "ikpso_contacts.h"
 #include "ikpso_coop.h"
 #include "ikpso_evaluate.h"
 #include "ikpso_gradient.h"

@@ -39,10 +39,11 @@ struct TermTrackOps {
 };
 
 // The evaluate kernels with units of their own (every Euler topology, both modes), likewise.  Kind
-// (ikpso_evaluate.h; ikpso_jacobian.h, ikpso_gradient.h) names the parameter block and the kernel:
+// (ikpso_evaluate.h; ikpso_jacobian.h, ikpso_gradient.h, ikpso_contacts.h) names the parameter block and the kernel:
 //   EvalOps<EvalFrames, ...>     ikpso_solver_evaluate_frames    ikpso_inst_evalframes_*.hip
 //   EvalOps<EvalJacobian, ...>   ikpso_solver_evaluate_jacobian  ikpso_inst_jacobian_*.hip
 //   EvalOps<EvalGradient, ...>   ikpso_solver_evaluate_gradient  ikpso_inst_gradient_*.hip
+//   EvalOps<EvalContacts, ...>   ikpso_solver_evaluate_contacts  ikpso_inst_contacts_*.hip
 template <class Kind, class Topo, int MODE>
 struct EvalOps {
     static hipError_t evaluate(const ChainHost& ch, const typename Kind::IO& io, hipStream_t stream);

@@ -10,7 +10,8 @@ from ._abi import (ARITH_FAST, ARITH_REFERENCE, COLLIDER_DTYPE, NODE, NODE_DTYPE
 from .scene import (RESET_TARGETS, EffectorNode, Node, OriginNode, Scene, TargetNode, check_distance,
                     init_colliders, reference_scene, serial_chain)
 from .solver import (MAIN_FITNESS, MAIN_PSO, BatchSolver, FitnessConfig, PSOConfig, calculate_pso,
-                     init_generators, init_generators_seeded, make_collider, manipulability, particles_tensor,
+                     contact_nodes, contact_pairs, init_generators, init_generators_seeded, make_collider, manipulability,
+                     particles_tensor,
                      rng_tensor, rotation_angle)
 from .dh import DHArm, dh_arm, dh_forward
 from .workloads import Workload, workload
@@ -20,5 +21,5 @@ __all__ = [
     "IkpsoError", "StaleLibraryError", "build_id", "load", "RESET_TARGETS", "EffectorNode", "Node", "OriginNode", "Scene", "TargetNode",
     "check_distance", "reference_scene", "serial_chain", "MAIN_FITNESS", "MAIN_PSO", "BatchSolver",
     "FitnessConfig", "PSOConfig", "calculate_pso", "init_generators", "init_generators_seeded", "manipulability",
-    "particles_tensor", "rng_tensor", "rotation_angle", "Workload", "workload", "DHArm", "dh_arm", "dh_forward",
+    "particles_tensor", "rng_tensor", "contact_nodes", "contact_pairs", "rotation_angle", "Workload", "workload", "DHArm", "dh_arm", "dh_forward",
 ]

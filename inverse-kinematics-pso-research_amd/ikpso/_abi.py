@@ -149,6 +149,7 @@ SIGNATURES = {
     "ikpso_solver_evaluate_frames": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ikpso_solver_evaluate_jacobian": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "ikpso_solver_evaluate_gradient": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ikpso_solver_evaluate_contacts": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp]),
     "ikpso_solver_generator_states": (_i32, [_vp, _i64, _i64, _vp, _vp]),
     "ikpso_solver_dof": (ctypes.c_int, [_vp]),
     "ikpso_solver_effectors": (ctypes.c_int, [_vp]),

@@ -132,6 +132,23 @@ def manipulability(jac, rows=slice(0, 3)) -> np.ndarray:
     return np.sqrt(np.maximum(np.linalg.det(j @ np.swapaxes(j, -1, -2)), 0.0))
 
 
+def contact_nodes(word) -> list:
+    """The node indices k (1 .. 32, ascending) whose bit k - 1 is set in one word of BatchSolver.contacts()."""
+    w = int(word) & 0xFFFFFFFF
+    return [k for k in range(1, 33) if (w >> (k - 1)) & 1]
+
+
+def contact_pairs(contacts) -> np.ndarray:
+    """Every contact of BatchSolver.contacts()' [n, C] words (a tensor or an array) as an int64 array [m, 3] of
+    (pose, collider, node) rows, sorted by pose, then collider, then node; node is the 1-based node index."""
+    c = contacts.detach().cpu().numpy() if hasattr(contacts, "detach") else np.asarray(contacts)
+    if c.ndim != 2:
+        raise ValueError("contacts must be [n, C]")
+    bits = (c.astype(np.int64)[:, :, None] >> np.arange(32, dtype=np.int64)) & 1
+    pose, coll, node = np.nonzero(bits)
+    return np.stack([pose, coll, node + 1], axis=1).astype(np.int64)
+
+
 def rng_tensor(count: int, device="cuda"):
     """Device buffer for `count` generator states (48 bytes each, curandState_t layout)."""
     torch = _torch()
@@ -222,6 +239,7 @@ class BatchSolver:
             boxes = _colliders(colliders)
             desc.colliders = _any_ptr(boxes, keep)
             desc.collider_count = int(boxes.shape[0])
+        self.colliders_given = int(desc.collider_count)  # the columns of contacts()
         handle = ctypes.c_void_p()
         _abi.check(self._lib.ikpso_solver_create(ctypes.byref(desc), ctypes.byref(handle)), "ikpso_solver_create")
         self._h = handle
@@ -564,6 +582,24 @@ class BatchSolver:
                                                             _stream_handle(stream)),
                    "ikpso_solver_evaluate_jacobian")
         return jac, pos
+
+    def contacts(self, angles, positions=False, stream=None):
+        """Which node hits which collider at given angle vectors (ikpso_solver_evaluate_contacts): an int32
+        tensor [n, C], C the colliders the solver was given (its own order, those left out as out of reach
+        included: all-zero columns); with positions=True, (contacts, node positions [n, J, 3]).  angles
+        [n, D] is evaluate()'s.  Bit k - 1 of contacts[i, c] is set when node k's node box or link box is
+        decided to intersect collider c -- the decision behind evaluate()'s FLT_MAX: (contacts != 0).any(1)
+        is exactly evaluate(...)[0] == FLT_MAX.  contact_nodes() and contact_pairs() decode the words.  Every
+        solver evaluate() serves is served."""
+        torch = _torch()
+        J, C = self.chain.shape[0] - 1, self.colliders_given
+        n, _ = self._evaluate_inputs(angles)
+        out = torch.empty((n, C), dtype=torch.int32, device=angles.device)
+        pos = torch.empty((n, J, 3), dtype=torch.float32, device=angles.device) if positions else None
+        _abi.check(self._lib.ikpso_solver_evaluate_contacts(self._h, _dev_ptr(angles), n, _dev_ptr(out) if C else None,
+                                                            _dev_ptr(pos), _stream_handle(stream)),
+                   "ikpso_solver_evaluate_contacts")
+        return (out, pos) if positions else out
 
     def gradient(self, angles, targets=None, rest=None, effector_rot=None, effector_rot_weight=None, stream=None):
         """The fitness evaluate_frames() reports and its gradient with respect to the angles
